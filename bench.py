@@ -26,10 +26,17 @@ max rank step time.  extra.headline_strong (N > 1) splits BASELINE's single
 (strong scaling).  RCCL carries only the barrier and the max-over-ranks of the
 timed wall.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-"roofline" (dominant kernel vs 8 TB/s HBM, per-launch kernel time from HIP
-events on the launch stream) and "cpu_baseline" (the CPU restatement of the
-reference's FusedCodecPipeline.read_sync timed on this host's cores).
+Prints ONE JSON line (rank 0).  A plain run does only what the headline figure
+needs: it builds the replicas, warms up, times the K steps and prints the
+driver's contract fields ("ms_per_step" = the max-over-ranks wall of the timed
+region / K) plus "roofline" (the headline kernel vs 8 TB/s HBM, from the event
+span of the same timed region).  `--dump-outputs DIR` also writes what the
+last timed step decoded to DIR/<name>.npy (dump_outputs), so two builds can be
+compared output for output.  `--full` adds everything that takes runs of its
+own: "extra" (the other BASELINE configs, `--extra`), "cpu_baseline" and the
+extras' "cpu_port" (the CPU restatement of the reference's
+FusedCodecPipeline.read_sync timed on this host's cores), and in "roofline"
+the eager per-launch kernel times and the PMC traffic.
 """
 
 from __future__ import annotations
@@ -1280,6 +1287,9 @@ def pmc_traffic():
 # ------------------------------------------------------------------------ main
 
 HEADLINE_KERNEL = ["?"]  # the decode kernel the library launched for the headline (zhip_last_kernel)
+HEADLINE_OUTS = []  # (out, this rank's batch items) of every headline replica, for --dump-outputs
+HEADLINE_FINITE = [None]  # full-shape bool array: where the headline's source is finite (all but the planted NaN)
+DUMP_MAX_BYTES = 32 << 20  # --dump-outputs: all ranks' files together stay under this
 
 
 def headline(ctx, args, weak: bool = False):
@@ -1304,9 +1314,12 @@ def headline(ctx, args, weak: bool = False):
     n_shards = 8 * rep
     mine_n = len(range(ctx.rank, n_shards, ctx.world))
     progs = []
+    HEADLINE_OUTS.clear()
+    HEADLINE_FINITE[0] = np.tile(np.isfinite(data), (rep, 1, 1))
     for r in range(args.replicas):
         prog, out, mine = build_partitioned(ctx, src, shape, inner, shards, "float32", 0.0,
                                             max(mine_n, 1) * (blob + 256) + (1 << 20))
+        HEADLINE_OUTS.append((out, mine))
         if r == 0:  # correctness gate: every decoded byte of this rank's shards
             prog.launch()
             prog.results()
@@ -1334,6 +1347,39 @@ def headline_strong(ctx, args):
                   workload="256x256x256 f32, 8/N shards of 128^3 per rank",
                   note="decoded_GiBps = the array's decoded bytes / max rank step time; "
                        "kernel_ms / hbm_frac are this rank's")
+
+
+def dump_outputs(ctx, steps: int, directory: str) -> None:
+    """--dump-outputs DIR: what the last timed step decoded, as float32 .npy.
+    The steps rotate over the replicas, so that is the out of replica
+    (steps - 1) mod replicas.  One GPU: ``headline_out.npy``, the decoded
+    array.  N ranks: ``headline_out_rank<r>.npy``, the rank's own shard regions
+    stacked in batch order (the rest of its full-shape out is never written).
+    An array over the byte budget is cut to a fixed sample: the elements at
+    sorted flat indices drawn without replacement by numpy's default_rng(0),
+    the same for every run and build.  The file holds finite values only, so
+    that two dumps compare with a plain tolerance: the positions where the
+    SOURCE is not finite (the planted NaN payload; chosen by the input, never
+    by what was decoded) are left out, which makes the file 1-D whenever one
+    falls into it.  The byte-exact check of those positions is the
+    correctness gate in headline()."""
+    out, mine = HEADLINE_OUTS[(steps - 1) % len(HEADLINE_OUTS)]
+    finite = HEADLINE_FINITE[0]
+    if ctx.world == 1:
+        name, a = "headline_out", out.cpu().numpy()
+    else:
+        name = f"headline_out_rank{ctx.rank}"
+        a = np.stack([out[tuple(it[3])].cpu().numpy() for it in mine])
+        finite = np.stack([finite[tuple(it[3])] for it in mine])
+    budget = DUMP_MAX_BYTES // ctx.world // a.itemsize
+    if a.size > budget:
+        idx = np.sort(np.random.default_rng(0).choice(a.size, budget, replace=False))
+        a, finite = a.reshape(-1)[idx], finite.reshape(-1)[idx]
+    if not finite.all():
+        a = a[finite]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), a)
+    log(f"[bench] wrote {name}.npy {a.shape} to {directory}")
 
 
 def free_port() -> int:
@@ -1382,6 +1428,14 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--replicas", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure too: the extra configs (--extra), the CPU "
+                         "baseline and ports, the eager per-launch kernel times and the PMC traffic of the "
+                         "roofline; a plain run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step decoded to DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of it when larger than 32 MiB; without the "
+                         "positions of the source's planted NaN, so every value is finite)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--tune", type=int, default=0,
                     help="kernel ablation bits (zhip_set_tuning; measurement experiments only)")
@@ -1396,8 +1450,9 @@ def main():
     ap.add_argument("--extra-cpu", default="cpu",
                     help="'cpu': time the CPU port of every config line too (N=1, rank 0); '' to skip")
     ap.add_argument("--extra", default="c1,c2,c3,c4,c5,enc,e2e,call,cpp",
-                    help="extra configs (subset of c1,c2,c3,c4,c5,enc,e2e,call,cpp, or ''); c4/c5 run "
-                         "partitioned at every N, the others at N=1")
+                    help="extra configs of a --full or --extra-only run (subset of "
+                         "c1,c2,c3,c4,c5,enc,e2e,call,cpp, or ''); c4/c5 run partitioned at every N, the "
+                         "others at N=1")
     args = ap.parse_args()
     if rank_plan(args.gpus, os.environ) == "launch":
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -1443,6 +1498,10 @@ def main():
         wall_max = ctx.max(wall)
     else:
         wall, wall_max, span_s = graph_steps(plist, args.steps, args.warmup, device, ctx)
+        kern_s = None
+    if args.dump_outputs:
+        dump_outputs(ctx, args.steps, args.dump_outputs)
+    if args.full and kern_s is None:
         # per-launch durations of the same kernel, eager (for the rocprof cross-check)
         kern_s = eager_kernel_times(plist, args.steps, device)
         for p in plist:
@@ -1454,7 +1513,6 @@ def main():
     # stream / steps (includes the graph's inter-launch gaps, so it is an upper
     # bound on the kernel duration and `achieved` a lower bound)
     avg_kern_s = span_s / args.steps
-    traffic, traffic_sha = pmc_traffic()
     achieved = (encoded + decoded) / avg_kern_s / 1e9
     res = {
         "metric": "decoded GiB/s (device-resident), sharded 256^3 f32 64^3 chunks, 1/2/4/8 GPU",
@@ -1486,26 +1544,31 @@ def main():
         },
         "roofline": {
             "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-            "traffic_lib_sha16": traffic_sha, "lib_sha16": lib_sha16(),
-            "traffic_source": TRAFFIC_JSON + " (FETCH_SIZE x2 + WRITE_SIZE per launch from "
-                              "separate rocprofv3 --pmc passes of this command)",
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
             "kernel": f"zhip::{HEADLINE_KERNEL[0]}<CRC,4,noswap> (zhip_decode_mapped)",
             "kernel_ms_avg": round(avg_kern_s * 1e3, 5),
-            "kernel_ms_eager_mean": round(float(np.mean(kern_s)) * 1e3, 5),
             "timing": "eager launches" if args.eager else
                       "hipGraph replay of the K launches; kernel_ms_avg = event span / K",
             "algorithmic_bytes_per_launch": encoded + decoded,
         },
     }
+    if kern_s is not None:
+        res["roofline"]["kernel_ms_eager_mean"] = round(float(np.mean(kern_s)) * 1e3, 5)
+    if args.full:
+        traffic, traffic_sha = pmc_traffic()
+        res["roofline"].update({
+            "traffic": traffic, "traffic_lib_sha16": traffic_sha, "lib_sha16": lib_sha16(),
+            "traffic_source": TRAFFIC_JSON + " (FETCH_SIZE x2 + WRITE_SIZE per launch from "
+                              "separate rocprofv3 --pmc passes of this command)"})
     del plist
+    HEADLINE_OUTS.clear()
     torch.cuda.empty_cache()
-    if args.extra:
+    if args.full and args.extra:
         log("[bench] extra configs " + args.extra)
         res["extra"] = extra_configs(ctx, args)
         if ctx.world > 1:
             res["extra"]["headline_strong"] = headline_strong(ctx, args)
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
+    if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
         log("[bench] cpu baseline")
         g = W.HEADLINE
         res["cpu_baseline"] = cpu_baseline(synthetic(g["shape"], seed=0), g["shape"], g["inner"],

@@ -4,6 +4,8 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 STEPS=${STEPS:-50}
+# the whole result (extras, CPU baseline, eager kernel times), not the plain headline run
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 timeout -k 10 600 python bench.py --steps "$STEPS" --warmup 10 ${BENCH_ARGS:-} > gpurun_out/bench.json 2> gpurun_out/bench.err
 rc=$?; echo "bench rc=$rc"; cat gpurun_out/bench.json; tail -3 gpurun_out/bench.err
 if [ $rc -ne 0 ]; then exit $rc; fi

@@ -3,7 +3,7 @@
 #   1. PMC passes of the headline (FETCH_SIZE, WRITE_SIZE: separate runs)
 #      -> $O/pmc_traffic.json, copied to profiles/r06/pmc_traffic.json so the
 #      bench below reports `traffic` for this library;
-#   2. the default bench.py line -> $O/bench.json;
+#   2. the bench.py --full line -> $O/bench.json;
 #   3. rocprofv3 --kernel-trace --stats of the headline and of each group of
 #      config lines (bench.py --extra-only --extra X) -> $O/prof/<run>/;
 #   4. scripts/rocprof_table.py -> $O/frac_table.json.
@@ -25,9 +25,9 @@ if [ "${SKIP_PMC:-0}" != "1" ]; then
   python scripts/pmc_summary.py "$O/pmc" k_decode "$O/pmc_traffic.json" || exit $?
   mkdir -p profiles/r06 && cp "$O/pmc_traffic.json" profiles/r06/pmc_traffic.json
 fi
-timeout -k 10 700 python -u bench.py > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 700 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err"
 rc=$?; echo "bench rc=$rc"; tail -c 300 "$O/bench.json"; echo; [ $rc -ne 0 ] && { tail -20 "$O/bench.err"; exit $rc; }
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof/hl" -o hl -- python bench.py --steps 50 --extra "" \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof/hl" -o hl -- python bench.py --full --steps 50 --extra "" \
   --no-cpu-baseline > "$O/prof/hl.json" 2> "$O/prof/hl.err"
 rc=$?; echo "rocprof hl rc=$rc"; [ $rc -ne 0 ] && { tail -20 "$O/prof/hl.err"; exit $rc; }
 for x in ${RUNS:-c1 c2 c3 c4 c5 enc cpp}; do

@@ -11,9 +11,9 @@ ZARR_HIP_ALLOW_LIB_OVERRIDE=1 ZHIP_LIB="$PWD/zarr-python_amd/zarr_hip/_lib/libza
   timeout -k 10 600 python -u -m pytest tests -m "gpu and tuning" -x -q -p no:cacheprovider --timeout 300 \
   --timeout-method thread > "$O/pytest_tuning.log" 2>&1
 rc=$?; echo "pytest tuning rc=$rc"; tail -3 "$O/pytest_tuning.log"; [ $rc -ne 0 ] && { tail -40 "$O/pytest_tuning.log"; exit $rc; }
-timeout -k 10 600 python -u bench.py > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 600 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err"
 rc=$?; echo "bench rc=$rc"; tail -c 400 "$O/bench.json"; [ $rc -ne 0 ] && { tail -20 "$O/bench.err"; exit $rc; }
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o hl -- python bench.py --steps 50 --extra "" \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o hl -- python bench.py --full --steps 50 --extra "" \
   --no-cpu-baseline > "$O/bench_prof.json" 2> "$O/bench_prof.err"
 rc=$?; echo "rocprof rc=$rc"; [ $rc -ne 0 ] && { tail -20 "$O/bench_prof.err"; exit $rc; }
 OUT=$O ROUNDS=15 CONFIGS="c3g" ARMS="prod=0:0,lb=0:62" bash scripts/gpu_arms.sh || exit $?
