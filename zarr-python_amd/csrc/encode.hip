@@ -830,6 +830,7 @@ int launch_encode(const EncodeParams& p, hipStream_t stream, int max_grid) {
         EncodeFn fn = pick_encode_quad(crc, p.g.itemsize, swap);
         if (!fn) return ZHIP_E_UNSUPPORTED;
         if (p.n_units == 0) return ZHIP_OK;
+        g_last_kernel = "k_encode_quad";
         hipLaunchKernelGGL(fn, dim3((p.n_units + 3u) / 4u), dim3(kThreads), 0, stream, p);
         return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
     }

@@ -1460,11 +1460,15 @@ class HipCodecPipeline:
                 with torch.cuda.device(device):
                     if not isinstance(value, torch.Tensor) or not value.is_cuda:  # one upload for all groups
                         value = _value_tensor(value, batch[0][1].dtype, device)
-                    for idx in groups:
-                        sub = [batch[i] for i in idx]
-                        spec = sub[0][1]
-                        ChunkWriter(self.codecs, spec, spec.shape, device).write(
-                            sub, value, self.codecs, drop_axes, partial_encode=partial_encode, pending=pend)
+                    try:
+                        for idx in groups:
+                            sub = [batch[i] for i in idx]
+                            spec = sub[0][1]
+                            ChunkWriter(self.codecs, spec, spec.shape, device).write(
+                                sub, value, self.codecs, drop_axes, partial_encode=partial_encode, pending=pend)
+                    except BaseException:
+                        pend.release()  # the groups already queued: nothing stored, regions given back
+                        raise
                     pend.finish(device)
                 return
             for idx in groups:  # one write per spec

@@ -462,6 +462,23 @@ def gather_sharded_partial(batch: list, sh, cps, n_inner: int, inner_shape, spec
                 raise
             return None
 
+    def short_read(raw_index):
+        """A range came back shorter than its index entry asked for: the store
+        clamped it at the blob's end, i.e. offset + length reaches past the
+        blob (the kernels' ZHIP_ST_INDEX_OOB, zhip_decode_common.h
+        resolve_unit).  A corrupted index that carries a CRC raises the
+        checksum message first, as the GPU's index check would."""
+        if sh.index_has_crc:
+            from .hoststage import host_crc32c
+            from .pipeline import crc_error_message
+
+            stored = int(np.frombuffer(raw_index, "<u4", count=1, offset=isz - 4)[0])
+            computed = host_crc32c(np.frombuffer(raw_index, np.uint8, count=isz - 4))
+            if stored != computed:
+                raise ValueError(crc_error_message(stored, computed))
+        raise ValueError("shard index entry points outside the shard blob")
+
+    index_raw = {}
     for k, s in shards.items():
         bg = s["bg"]
         st = getattr(bg, "store", None)
@@ -475,6 +492,7 @@ def gather_sharded_partial(batch: list, sh, cps, n_inner: int, inner_shape, spec
         if len(raw) < isz:
             raise ValueError("shard blob is shorter than its index")
         idx = np.frombuffer(raw, dtype="<u8", count=2 * n_inner).reshape(n_inner, 2)
+        index_raw[k] = raw
         if inner_decode is not None and sh.index_has_crc:
             # the offsets drive host decompression before the GPU sees the
             # index: verify it here first, as _decode_shard_index_sync does
@@ -534,6 +552,9 @@ def gather_sharded_partial(batch: list, sh, cps, n_inner: int, inner_shape, spec
                 out_of_shard[k] = None
                 continue
             bufs = [staged_host(buf) for _, buf in got]
+            for (j, _), buf in zip(got, bufs):
+                if len(buf) < fetch[j][2]:
+                    short_read(raw)
             if inner_decode is not None:
                 bufs = inner_decode(bufs)
             top = pieces[-1][1] + ((pieces[-1][2] + A) & ~A) if pieces else lo
@@ -571,6 +592,8 @@ def gather_sharded_partial(batch: list, sh, cps, n_inner: int, inner_shape, spec
                     m = len(buf)
                     if m > size:
                         raise ValueError("an inner chunk is larger than its index entry")
+                    if m < size:
+                        short_read(index_raw[k])
                     pieces.append((buf, off, m))
                     src_by[slot], len_by[slot], miss_by[slot] = off, m, False
                 pieces.sort(key=lambda x: x[1])  # packing jobs take pieces in destination order

@@ -119,32 +119,47 @@ class PendingWrites:
     def __init__(self):
         self.items = []  # (dest, setters, [(EncodeLaunch, idx)], elen, keep_all, prototype, [DecodeProgram])
 
+    def release(self) -> None:
+        """Drop every queued group: nothing is stored, reserved regions go back."""
+        for it in self.items:
+            it[0].release()
+        self.items = []
+
     def finish(self, device) -> None:
         from .pipeline import _RangeSet
 
-        rngs, shape = [], []
-        for dest, setters, launches, elen, keep, proto, checks in self.items:
-            for prog in checks:
-                r = prog.wait_ranges()
-                rngs += r
-                shape.append(("check", sum(x[1] for x in r) // 4))
-            for l, _ in launches:
-                rngs.append((l.d_nonempty.data_ptr(), 4 * l.n))
-                shape.append(("ne", l.n))
-        host = _RangeSet(rngs).wait(device).copy() if rngs else np.zeros(0, np.uint32)
-        pos, k = 0, 0
-        for dest, setters, launches, elen, keep, proto, checks in self.items:
-            for prog in checks:
-                n = shape[k][1]
-                prog.results_from_words(host[pos: pos + n])  # raises like the reference
-                pos += n
-                k += 1
-            ne = np.zeros(len(setters), bool)
-            for l, idx in launches:
-                ne[idx] = host[pos: pos + l.n] != 0
-                pos += l.n
-                k += 1
-            dest.finish(setters, [elen if (keep or ne[i]) else 0 for i in range(len(setters))], proto)
+        try:
+            rngs, shape = [], []
+            for dest, setters, launches, elen, keep, proto, checks in self.items:
+                for prog in checks:
+                    r = prog.wait_ranges()
+                    rngs += r
+                    shape.append(("check", sum(x[1] for x in r) // 4))
+                for l, _ in launches:
+                    rngs.append((l.d_nonempty.data_ptr(), 4 * l.n))
+                    shape.append(("ne", l.n))
+            host = _RangeSet(rngs).wait(device).copy() if rngs else np.zeros(0, np.uint32)
+            # every group's checks first (an error raises with nothing stored) ...
+            pos, k = 0, 0
+            lengths = []
+            for dest, setters, launches, elen, keep, proto, checks in self.items:
+                for prog in checks:
+                    n = shape[k][1]
+                    prog.results_from_words(host[pos: pos + n])  # raises like the reference
+                    pos += n
+                    k += 1
+                ne = np.zeros(len(setters), bool)
+                for l, idx in launches:
+                    ne[idx] = host[pos: pos + l.n] != 0
+                    pos += l.n
+                    k += 1
+                lengths.append([elen if (keep or ne[i]) else 0 for i in range(len(setters))])
+            # ... then the commits
+            for (dest, setters, launches, elen, keep, proto, checks), ln in zip(self.items, lengths):
+                dest.finish(setters, ln, proto)
+        except BaseException:
+            self.release()
+            raise
         self.items = []
 
 
@@ -197,6 +212,7 @@ class _Dest:
             self.store = setters[0].store
         self.reserved = int(nbytes_each)
         self.offs = []
+        self.done = 0  # offs[:done] are committed (or given back)
         if self.store is not None:
             self.lock = self.store.arena.lock
             self.lock.acquire()
@@ -216,6 +232,16 @@ class _Dest:
             self.lock.release()
             self.lock = None
 
+    def release(self):
+        """An error before (or during) finish: the arena regions not yet
+        committed go back to the arena, so a failed write leaks nothing."""
+        self.release_lock()
+        if self.store is not None:
+            with self.store.arena.lock:
+                for off in self.offs[self.done:]:
+                    self.store.arena.free(off, max(self.reserved, 1))
+        self.done = len(self.offs)
+
     def finish(self, setters, lengths, prototype):
         """Store / delete each setter's result (length 0 = elided)."""
         self.release_lock()
@@ -227,6 +253,7 @@ class _Dest:
             if self.store is not None:
                 if n == 0:
                     s.delete_sync()
+                self.done = i + 1  # (commit gives an elided region back itself)
                 self.store.commit(s.path, self.offs[i], n, self.reserved)
             elif n == 0:
                 s.delete_sync()
@@ -365,6 +392,16 @@ class ChunkWriter:
             if r["code"] == N.ST_INDEX_OOB:
                 raise ValueError("shard index entry points outside the shard blob")
             raise ValueError("encoded chunk length does not match the fixed-size codec chain")
+        # an untouched inner chunk whose index entry is out of bounds or not of
+        # the chain's length: the reference carries the slice over as stored,
+        # the fixed-size packer cannot, so the write is refused
+        # before anything is reserved or stored
+        for i, s in repairs:
+            code = codes[(item_of == i) & (slot_of == s)][0]
+            if code == N.ST_INDEX_OOB:
+                raise ValueError("shard index entry points outside the shard blob")
+            if code != N.ST_CRC_MISMATCH:
+                raise ValueError("encoded chunk length does not match the fixed-size codec chain")
         return st, repairs
 
     def _encode_chunks(self, complete_items, partial_items, v, temp, pending=None, checks=()):
@@ -401,18 +438,25 @@ class ChunkWriter:
                                  [base + i for i in range(len(partial_items))]))
             for l, _ in launches:
                 l.launch()
+        except BaseException:
+            dest.release()
+            raise
         finally:
             dest.release_lock()
         if pending is not None:  # committed by PendingWrites.finish after one readback
             pending.items.append((dest, setters, launches, elen, spec.config.write_empty_chunks, spec.prototype,
                                   list(checks)))
             return
-        nonempty = np.zeros(len(setters), bool)
-        for l, idx in launches:
-            nonempty[idx] = l.nonempty()
-        keep_all = spec.config.write_empty_chunks
-        lengths = [elen if (keep_all or nonempty[i]) else 0 for i in range(len(setters))]
-        dest.finish(setters, lengths, spec.prototype)
+        try:
+            nonempty = np.zeros(len(setters), bool)
+            for l, idx in launches:
+                nonempty[idx] = l.nonempty()
+            keep_all = spec.config.write_empty_chunks
+            lengths = [elen if (keep_all or nonempty[i]) else 0 for i in range(len(setters))]
+            dest.finish(setters, lengths, spec.prototype)
+        except BaseException:
+            dest.release()
+            raise
 
     def _encode_shards(self, complete_items, partial_items, v, temp, present, partial_encode,
                        repairs=(), raws=None):
@@ -513,6 +557,11 @@ class ChunkWriter:
                     raw = _host_bytes(raws[i])
                     ib = raw[:index_size] if sh.index_location == "start" else raw[len(raw) - index_size:]
                     off, ln = (int(x) for x in np.frombuffer(ib[: 16 * n_inner].tobytes(), "<u8").reshape(n_inner, 2)[s])
+                    # (_check_partial_merge lets only CRC mismatches through: the
+                    # entry is in bounds and of the chain's length; checked again
+                    # here so a bad one can never reach the copy)
+                    if off + ln > len(raw):
+                        raise ValueError("shard index entry points outside the shard blob")
                     if ln != elen:
                         raise ValueError("encoded chunk length does not match the fixed-size codec chain")
                     at = int(offs[base + i]) + data_start + int(rank_of_slot[s]) * elen
@@ -541,7 +590,14 @@ class ChunkWriter:
                                             nonempty.data_ptr(), d_newrank.data_ptr(), d_rank.data_ptr(),
                                             d_blen.data_ptr(), _stream_handle(self.device)),
                     "zhip_shard_pack")
+        except BaseException:
+            dest.release()
+            raise
         finally:
             dest.release_lock()
-        blen = d_blen[: len(setters)].cpu().numpy()
-        dest.finish(setters, blen, spec.prototype)
+        try:
+            blen = d_blen[: len(setters)].cpu().numpy()
+            dest.finish(setters, blen, spec.prototype)
+        except BaseException:
+            dest.release()
+            raise
