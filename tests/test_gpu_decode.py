@@ -150,9 +150,14 @@ def test_duo_kernel_cases(device, case):
 
 
 def test_duo_crc_mismatch(device):
-    """A corrupted chunk of > 32 units (the duo kernel by default) raises the
-    reference's message."""
+    """A corrupted chunk of > 32 units raises the reference's message.  These
+    2 MiB chunks have 64 units, a multiple of 8, and the launch has 128 units
+    (at most 512): since round 5 that is k_decode_ilw512, not k_decode_duo,
+    which now takes only chunks of more than 32 units whose unit count is no
+    multiple of 8 (its corruption cases: tests/test_gpu_kernel_matrix.py,
+    duo_33 / duo_ragged)."""
     import zarr_hip
+    from zarr_hip import _native as N
 
     meta = O.ArrayMeta((1024, 1024), (512, 1024), np.dtype("float32"), 0.0, codecs=[LE, CRC])
     host = {}
@@ -169,6 +174,7 @@ def test_duo_crc_mismatch(device):
     with pytest.raises(ValueError) as got:
         arr[...]
     assert str(got.value) == str(want.value)
+    assert N.lib().zhip_last_kernel().decode() == "k_decode_ilw512"
 
 
 def test_bytes_only_no_crc(device):
@@ -1414,9 +1420,16 @@ def test_il_split_publication_arm(device, arm):
         set_tuning(6, 0)
 
 
+def _il_first_step(r, S):
+    """k_decode_il: workgroup r of a chunk takes steps (r / S) S 8 + r % S + S k (k < 8)."""
+    return (r // S) * S * 8 + r % S
+
+
 LB_CASES = {  # arm -> (shape, kernel, positions per chunk, byte offset of position p in a chunk)
-    # k_decode_il: workgroup r takes steps 64 (r / 8) + r % 8 + 8 k (S = 8)
-    58: ((256, 256, 128), "k_decode_il", 32, lambda p: 4096 * (64 * (p // 8) + p % 8) + 2000),
+    # k_decode_il, 1 MiB chunks (32 units): zhip_decode_mapped takes the widest interleave the plan built,
+    # S = 32 (arm 58 is none of the arms 69 / 70 / 71 that force another), one group of 32 workgroups, so
+    # workgroup p takes steps p + 32 k and its first step is step p: offset 4096 p + 2000
+    58: ((256, 256, 128), "k_decode_il", 32, lambda p: 4096 * _il_first_step(p, 32) + 2000),
     # k_decode_ilw512 (the N = 8 share's shape): unit r takes steps 8 r .. 8 r + 7
     "58w": ((128, 128, 128), "k_decode_ilw512", 32, lambda p: 4096 * 8 * p + 2000),
     # k_decode_ilh: half unit u takes steps 8 (u / 2) + 4 (u % 2) .. + 3

@@ -62,8 +62,17 @@ def test_fdiv_python_matches_native(d):
         assert N.lib().zhip_fdiv_eval(n, d) == n // d
 
 
+# Chunk sizes of the production row kernels' matrix (tests/test_gpu_kernel_matrix.py):
+# ragged heads (a first 4 KiB step before the chunk start) at S = 8 (252 KiB,
+# also 7 bytes short of it) and S = 32 (1000 KiB, also 5 bytes past it, six
+# such steps), S = 16 (504 KiB ragged), three groups of eight (768 KiB), the
+# counted publication's 40 / 48 / 64 units, and 33 units (1056 KiB, and
+# 1036 KiB ragged): no interleaved form, the pair / duo kernels' frame.
+MATRIX_SIZES = [258048, 258041, 516096, 786432, 1024000, 1024005, 1310720, 1572864, 2097152, 1081344, 1060864]
+
+
 @pytest.mark.parametrize("n", [0, 1, 5, 16, 31, 4096, 4100, 32767, 32768, 32769, 65536 + 12,
-                               1048576])
+                               1048576] + MATRIX_SIZES)
 def test_emulated_kernel_crc_matches_oracle(n):
     """The device decomposition (units end-aligned at align16(N), per-thread Horner
     over 4 KiB strides, per-thread and per-unit shift constants, XOR combine, R->N
@@ -210,14 +219,19 @@ def test_host_copy_pool(n):
         assert dst.tobytes() == src.tobytes()
 
 
-@pytest.mark.parametrize("n", [65536, 126976, 131072, 196608, 524288, 1048576, 2 ** 21, 3 * 2 ** 20, 4100, 65552])
+@pytest.mark.parametrize("n", [65536, 126976, 131072, 196608, 524288, 1048576, 2 ** 21, 3 * 2 ** 20, 4100, 65552] +
+                         [m for m in MATRIX_SIZES if m != 2 ** 21])
 def test_emulated_interleaved_crc_matches_oracle(n):
     """k_decode_il's decomposition (a workgroup's eight 4 KiB steps at a stride
     of S steps, A_(4096 S) tables, per-workgroup lane constants with negative
     shifts where the stride outruns the chunk end) reproduces crc32c, with the
     interleave the decode takes (the widest of S = 32 / 16 / 8 that tiles the
     steps: 1 MiB chunks S = 32, 512 KiB S = 16); layouts whose step count no
-    group of S x 8 steps tiles have no interleaved form."""
+    group of S x 8 steps tiles have no interleaved form.  MATRIX_SIZES adds
+    ragged heads at the production interleaves -- 252 KiB under S = 8 (one
+    step before the chunk start), 1000 KiB under S = 32 (six, one in each of
+    workgroups 0-5), 504 KiB under S = 16 -- which must contribute nothing,
+    and the chunks of 24 / 40 / 48 / 64 units."""
     from zarr_hip import _native as N
 
     rng = np.random.default_rng(n)
@@ -236,7 +250,7 @@ def test_emulated_interleaved_crc_matches_oracle(n):
         assert got == O.crc32c(data)
 
 
-@pytest.mark.parametrize("n", [4096, 32768, 65536, 131072, 1048576, 4100, 65552, 2 ** 21 + 4096])
+@pytest.mark.parametrize("n", [4096, 32768, 65536, 131072, 1048576, 4100, 65552, 2 ** 21 + 4096] + MATRIX_SIZES)
 def test_emulated_xw_crc_matches_oracle(n):
     """k_decode_xw's decomposition (lane l of 8 KiB span r: eight blocks 1 KiB
     apart through the A_1024 tables, per-(span, lane) constants, negative

@@ -234,6 +234,20 @@ int zhip_device_count(void) {
 
 static void plan_affine(zhip_plan* p);
 
+// The one rule for k_decode_il / k_encode_il's wider interleave: groups of
+// S x 8 steps (S = 16 / 32) must tile the chunk's steps, and only plans whose
+// own groups are eight wide widen (il_S = 2 / 4: the tuning arms' narrow
+// groups keep theirs).  zhip_plan_upload builds a table set (off_il_s) for
+// every S that tiles; the launches and zhip_emulate_chunk_crc_il take the
+// widest.
+static bool il_tiles(const zhip_plan* p, uint32_t S) {
+    return p->il_S == 8u && ((uint64_t)p->nseg * kDefaultBlocks) % ((uint64_t)S * kDefaultBlocks) == 0;
+}
+
+static uint32_t il_widest(const zhip_plan* p) {
+    return il_tiles(p, 32u) ? 32u : il_tiles(p, 16u) ? 16u : p->il_S;
+}
+
 int zhip_plan_create(const zhip_layout* layout, zhip_plan** out) {
     std::call_once(g_once, init_tables);
     if (!layout || !out) return set_err(ZHIP_E_INVALID, "null argument");
@@ -371,13 +385,13 @@ int zhip_plan_upload(zhip_plan* p) {
     const size_t n_ilh = (ilw && p->il_S == 8u && 2 * p->nseg <= 64u) ? (size_t)2 * p->nseg * kThreads : 0;
     // k_decode_il's wider interleave (round 6): groups of 16 / 32 workgroups, the
     // same tables and constants for strides S = 16 / 32 where the chunk's steps
-    // tile them (the decode takes the widest, il_decode_S; k_encode_il keeps
-    // S = 8; tuning arms 69 / 70 / 71 force 16 / 32 / 8).  Graph-timed on the
+    // tile them (il_tiles; the decode and k_encode_il take the widest,
+    // il_widest; tuning arms 69 / 70 / 71 force 16 / 32 / 8).  Graph-timed on the
     // headline: S = 32 25.49 / 25.33 us vs 25.76 / 25.76 for S = 8 in two
     // interleaved pairs (profiles/r06/f/)
     size_t n_ils[2] = {0, 0};
-    for (int i = 0; i < 2 && p->il_S == 8u; ++i)
-        if (((uint64_t)p->nseg * kDefaultBlocks) % ((16u << i) * (uint64_t)kDefaultBlocks) == 0) n_ils[i] = n_il;
+    for (int i = 0; i < 2; ++i)
+        if (il_tiles(p, 16u << i)) n_ils[i] = n_il;
     std::vector<uint32_t> h(n_old + n_pair + n_il + n_xw + n_ilw[0] + n_ilw[1] + n_ilh + n_ils[0] + n_ils[1]);
     build_horner(h.data());
     for (int t = 0; t < kThreads; ++t) h[4096 + t] = xpow8((uint64_t)kWgStride - 16u * t);
@@ -1546,9 +1560,7 @@ uint32_t zhip_emulate_chunk_crc_il(const zhip_plan* plan, const uint8_t* data) {
     if (!plan || !plan->il_S) return 0xFFFFFFFFu;
     // the interleave the decode launches take (zhip_decode_mapped): the widest
     // that tiles the chunk's steps (the rule zhip_plan_upload builds tables by)
-    uint32_t S = plan->il_S;
-    const uint64_t n_st = (uint64_t)plan->nseg * kDefaultBlocks;
-    if (S == 8u) S = n_st % (32ull * kDefaultBlocks) == 0 ? 32u : n_st % (16ull * kDefaultBlocks) == 0 ? 16u : 8u;
+    const uint32_t S = il_widest(plan);
     const uint32_t K = kDefaultBlocks;
     std::vector<uint32_t> tab(kPairTabWords);
     build_pair_tables(tab.data(), (uint64_t)kWgStride * S);

@@ -822,6 +822,7 @@ int launch_encode(const EncodeParams& p, hipStream_t stream, int max_grid) {
         const uint64_t gpc = (p.t_per_chunk + 3u) / 4u;  // four tiles per workgroup
         if ((uint64_t)p.n_chunks * gpc >= (1ull << 31) || gpc >= 65536u) return ZHIP_E_UNSUPPORTED;
         // (the last arrival of each chunk writes its non-empty flag)
+        g_last_kernel = "k_encode_tile";
         hipLaunchKernelGGL(fn, dim3((uint32_t)(p.n_chunks * gpc)), dim3(kThreads), 0, stream, p);
         return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
     }
@@ -876,6 +877,7 @@ int launch_encode(const EncodeParams& p, hipStream_t stream, int max_grid) {
         max_grid = (max_grid / 8) * per_cu;
     if (g_tune_max_grid > 0) max_grid = g_tune_max_grid;
     const uint32_t grid = p.n_units < (uint32_t)max_grid ? p.n_units : (uint32_t)max_grid;
+    g_last_kernel = "k_encode";
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), 0, stream, p);
     return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
 }
