@@ -31,6 +31,13 @@
  *                     chunk_is_empty (chunk_utils.py:74-85, buffer/core.py:534-558).
  *   zhip_shard_pack   ShardingCodec._build_shard_layout / _assemble_shard /
  *                     _encode_shard_index_sync (sharding.py:887-950, 633-640).
+ *   zhip_select_copy  the numpy fancy indexing of orthogonal / coordinate / mask
+ *                     selections on decoded chunks: scatter_chunk's
+ *                     out[out_selection] = chunk[chunk_selection] and
+ *                     _merge_chunk_array's chunk[chunk_selection] = value[out_selection]
+ *                     (chunk_utils.py:88-162) for the projections of
+ *                     OrthogonalIndexer / CoordinateIndexer / MaskIndexer
+ *                     (src/zarr/core/indexing.py:625-1046, 1171-1373).
  *   zhip_plan_*       host-side constant tables (no reference counterpart:
  *                     the CRC-combine operators the GPU kernels need).
  *
@@ -518,6 +525,66 @@ int zhip_shard_pack(const zhip_plan *plan, void *dst, const zhip_shard *d_shards
                     uint32_t n_inner, uint32_t elen, uint32_t index_size, uint32_t pack_flags,
                     const uint32_t *d_nonempty, uint32_t *d_newrank, const uint32_t *d_rank_of_slot,
                     uint64_t *d_blob_len, void *stream);
+
+/* ---- element gather / scatter of non-basic selections ----
+ *
+ * zhip_select_copy replaces the numpy fancy indexing the reference runs on
+ * host chunks for orthogonal, coordinate and mask selections
+ * (OrthogonalIndexer / CoordinateIndexer / MaskIndexer projections,
+ * src/zarr/core/indexing.py:625-1046, 1171-1373, applied by scatter_chunk and
+ * _merge_chunk_array, src/zarr/core/chunk_utils.py:88-162):
+ *   read   out[out_selection] = chunk[chunk_selection]     a = decoded chunks, b = out
+ *   write  chunk[chunk_selection] = value[out_selection]   a = value, b = decoded chunks
+ *
+ * The separable table form.  An item is a product of up to ZHIP_MAX_DIMS
+ * dimensions; its element (k_0 .. k_{n-1}), 0 <= k_d < count_d, is read at
+ * a + a_base + sum_d A_d[k_d] and written at b + b_base + sum_d B_d[k_d] (int64
+ * byte offsets).  A dimension is affine, A_d[k] = a0 + k sa and B_d[k] = b0 + k sb
+ * (slices, integers: no table traffic), or a table: pairs (A_d[k], B_d[k]) at
+ * table[2 (table_off + k)], table[2 (table_off + k) + 1] of one shared int64
+ * array.  Orthogonal selections use one dimension per chunk dimension;
+ * coordinate and mask selections one table dimension of n points.  Elements
+ * are numbered with the LAST dimension fastest, so consecutive lanes walk the
+ * innermost dimension. */
+#define ZHIP_SELECT_TILE 1024u  /* elements of one workgroup (256 lanes x 4); a tile never spans two items */
+
+typedef struct zhip_select_dim {
+    int64_t a0, sa;      /* affine form */
+    int64_t b0, sb;
+    uint64_t table_off;  /* table form: index of the dimension's first pair */
+    uint32_t count;      /* >= 1 */
+    uint32_t table;      /* 0 affine, 1 table */
+    zhip_fdiv div;       /* division by count */
+    uint32_t _pad[2];
+} zhip_select_dim;       /* 64 bytes */
+
+typedef struct zhip_select_item {
+    int64_t a_base, b_base;
+    uint32_t ndim;       /* 1 .. ZHIP_MAX_DIMS */
+    uint32_t total;      /* prod(count) < 2^31 */
+    uint32_t _pad[2];
+    zhip_select_dim dims[ZHIP_MAX_DIMS];
+} zhip_select_item;      /* 544 bytes */
+
+/* One launch over every item.  d_tile_prefix[i] = tiles of the items before i
+ * (n_items + 1 words, the last = n_tiles; item i has
+ * ceil(total_i / ZHIP_SELECT_TILE) tiles).  itemsize is 1, 2, 4 or 8; a and b
+ * are aligned to it and do not overlap; a_size / b_size are the bytes readable
+ * at a / writable at b.  THE CALLER VALIDATES THE TABLES (every offset inside
+ * its buffer): the kernel only skips an element whose offsets fall outside
+ * a_size / b_size, as a second fence.  Asynchronous on `stream`; afterwards
+ * zhip_last_kernel() is "k_select_copy". */
+int zhip_select_copy(const zhip_select_item *d_items, uint32_t n_items, const int64_t *d_table,
+                     const uint32_t *d_tile_prefix, uint32_t n_tiles, const void *a, uint64_t a_size,
+                     void *b, uint64_t b_size, uint32_t itemsize, void *stream);
+/* CPU-only test hook: the same tile walk and the same address arithmetic (one
+ * shared host/device function) over host memory.  Also validates the host
+ * tables (counts, divisors, prefix) and returns ZHIP_E_INVALID for bad ones;
+ * returns ZHIP_E_BOUNDS, copying nothing further, at the first element outside
+ * a_size / b_size. */
+int zhip_emulate_select_copy(const zhip_select_item *items, uint32_t n_items, const int64_t *table,
+                             uint64_t table_pairs, const uint32_t *tile_prefix, uint32_t n_tiles,
+                             const void *a, uint64_t a_size, void *b, uint64_t b_size, uint32_t itemsize);
 
 /* Host CRC-32C (reflected 0x82F63B78, init / xorout 0xFFFFFFFF) of nbytes at
  * data: the host stage of a chain, where the bytes never reach the GPU -- a

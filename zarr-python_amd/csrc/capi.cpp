@@ -16,6 +16,7 @@
 #include "../../include/zarrhip.h"
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
+#include "zhip_select.h"
 
 using namespace zhip;
 
@@ -1450,6 +1451,73 @@ int zhip_shard_pack(const zhip_plan* plan, void* dst, const zhip_shard* d_shards
 uint32_t zhip_fdiv_eval(uint32_t n, uint32_t d) {
     const zhip_fdiv f = make_fdiv(d);
     return fdiv_apply(n, f.m, f.s);
+}
+
+// ---- zhip_select_copy: gather / scatter of non-basic selections (select.hip) ----
+static int select_args(uint32_t n_items, const void* items, const void* prefix, const void* a, const void* b,
+                       uint32_t itemsize) {
+    if (itemsize != 1 && itemsize != 2 && itemsize != 4 && itemsize != 8)
+        return set_err(ZHIP_E_UNSUPPORTED, "itemsize must be 1, 2, 4 or 8");
+    if (!n_items || !items || !prefix || !a || !b) return set_err(ZHIP_E_INVALID, "null argument");
+    if (((uintptr_t)a | (uintptr_t)b) & (itemsize - 1)) return set_err(ZHIP_E_INVALID, "a / b not aligned to itemsize");
+    return ZHIP_OK;
+}
+
+int zhip_select_copy(const zhip_select_item* d_items, uint32_t n_items, const int64_t* d_table,
+                     const uint32_t* d_tile_prefix, uint32_t n_tiles, const void* a, uint64_t a_size, void* b,
+                     uint64_t b_size, uint32_t itemsize, void* stream) {
+    if (n_tiles == 0) return ZHIP_OK;
+    const int rc = select_args(n_items, d_items, d_tile_prefix, a, b, itemsize);
+    if (rc != ZHIP_OK) return rc;
+    if (n_tiles > 0x7fffffffu) return set_err(ZHIP_E_UNSUPPORTED, "too many tiles for one launch");
+    const int e = select_launch(d_items, n_items, d_table, d_tile_prefix, n_tiles, a, a_size, b, b_size, itemsize, stream);
+    if (e != 0) return set_err(ZHIP_E_HIP, std::string("k_select_copy launch: ") + hipGetErrorString((hipError_t)e));
+    return ZHIP_OK;
+}
+
+// The kernel's walk on the host: every tile, its item by the same prefix
+// search, its kSelThreads x kSelPer element slots in the kernel's order, the
+// same offsets.  Checks the tables a caller could get wrong first.
+int zhip_emulate_select_copy(const zhip_select_item* items, uint32_t n_items, const int64_t* table,
+                             uint64_t table_pairs, const uint32_t* tile_prefix, uint32_t n_tiles, const void* a,
+                             uint64_t a_size, void* b, uint64_t b_size, uint32_t itemsize) {
+    if (n_tiles == 0) return ZHIP_OK;
+    const int rc = select_args(n_items, items, tile_prefix, a, b, itemsize);
+    if (rc != ZHIP_OK) return rc;
+    if (tile_prefix[0] != 0 || tile_prefix[n_items] != n_tiles) return set_err(ZHIP_E_INVALID, "tile prefix ends");
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const zhip_select_item& it = items[i];
+        if (it.ndim < 1 || it.ndim > ZHIP_MAX_DIMS) return set_err(ZHIP_E_INVALID, "item ndim");
+        uint64_t total = 1;
+        for (uint32_t d = 0; d < it.ndim; ++d) {
+            const zhip_select_dim& D = it.dims[d];
+            if (D.count < 1 || D.count >= (1u << 31)) return set_err(ZHIP_E_INVALID, "dimension count");
+            const zhip_fdiv f = make_fdiv(D.count);
+            if (f.m != D.div.m || f.s != D.div.s) return set_err(ZHIP_E_INVALID, "dimension divisor");
+            if (D.table && (!table || D.table_off + D.count > table_pairs))
+                return set_err(ZHIP_E_INVALID, "dimension table range");
+            total *= D.count;
+            if (total >= (1ull << 31)) return set_err(ZHIP_E_INVALID, "item total");
+        }
+        if (total != it.total) return set_err(ZHIP_E_INVALID, "item total != prod(count)");
+        if (tile_prefix[i + 1] - tile_prefix[i] != (it.total + ZHIP_SELECT_TILE - 1) / ZHIP_SELECT_TILE)
+            return set_err(ZHIP_E_INVALID, "tile prefix step");
+    }
+    for (uint32_t tile = 0; tile < n_tiles; ++tile) {
+        const uint32_t ii = select_find_item(tile_prefix, n_items, tile);
+        const zhip_select_item& it = items[ii];
+        for (uint32_t t = 0; t < kSelThreads; ++t)
+            for (uint32_t j = 0; j < kSelPer; ++j) {
+                const uint32_t e = (tile - tile_prefix[ii]) * ZHIP_SELECT_TILE + t + j * kSelThreads;
+                if (e >= it.total) continue;
+                int64_t ao, bo;
+                select_addr(it, table, e, ao, bo);
+                if (!select_inside(ao, bo, a_size, b_size, itemsize))
+                    return set_err(ZHIP_E_BOUNDS, "element offset outside its buffer");
+                memcpy((uint8_t*)b + bo, (const uint8_t*)a + ao, itemsize);
+            }
+    }
+    return ZHIP_OK;
 }
 
 // CPU emulation of the device CRC combine for one chunk of a plan (the exact

@@ -165,6 +165,15 @@ E_BOUNDS = -5
 ROWBLK_DT = np.dtype([("rel", "<i4"), ("lo", "<u2"), ("hi", "<u2")])
 
 
+# zhip_select_dim / zhip_select_item (include/zarrhip.h): zhip_select_copy's table form
+SELECT_TILE = 1024
+SELECT_DIM_DT = np.dtype([("a0", "<i8"), ("sa", "<i8"), ("b0", "<i8"), ("sb", "<i8"), ("table_off", "<u8"),
+                          ("count", "<u4"), ("table", "<u4"), ("div", "<u4", (2,)), ("_pad", "<u4", (2,))])
+SELECT_ITEM_DT = np.dtype([("a_base", "<i8"), ("b_base", "<i8"), ("ndim", "<u4"), ("total", "<u4"),
+                           ("_pad", "<u4", (2,)), ("dims", SELECT_DIM_DT, (MAX_DIMS,))])
+assert SELECT_DIM_DT.itemsize == 64 and SELECT_ITEM_DT.itemsize == 544
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -277,6 +286,10 @@ def lib():
     L.zhip_fdiv_eval.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.zhip_fdiv_eval.restype = ctypes.c_uint32
     L.zhip_tuning_build.restype = ctypes.c_int
+    L.zhip_select_copy.argtypes = [vp, u32, vp, vp, u32, vp, u64, vp, u64, u32, vp]
+    L.zhip_select_copy.restype = ctypes.c_int
+    L.zhip_emulate_select_copy.argtypes = [vp, u32, vp, u64, vp, u32, vp, u64, vp, u64, u32]
+    L.zhip_emulate_select_copy.restype = ctypes.c_int
     if L.zhip_abi_version() != 1:
         raise NativeError("libzarrhip ABI version mismatch")
     if L.zhip_tuning_build() and not _override_allowed():

@@ -21,8 +21,9 @@ import numpy as np
 from . import buffer
 from .codecs import BytesCodec, Crc32cCodec, ShardingCodec, parse_codecs
 from .grid import ChunkGrid
-from .indexing import basic_projections, chunk_batch
-from .pipeline import DecodeProgram, HipCodecPipeline
+from .indexing import (CoordinateIndexer, MaskIndexer, OrthogonalIndexer, basic_projections, chunk_batch,
+                       is_bool_array, is_pure_fancy_indexing, is_pure_orthogonal_indexing)
+from .pipeline import BasicBatch, DecodeProgram, HipCodecPipeline
 from .spec import ArrayConfig, ArraySpec
 from .store import DeviceStore, StorePath
 
@@ -222,13 +223,13 @@ class Array:
         if key is not None:
             hit = cache.get(key)
             if hit is not None:
-                return list(hit[0]), hit[1]
+                return BasicBatch(hit[0]), hit[1]
         batch, out_shape = self._batch_info(selection)
         if key is not None:
             if len(cache) >= 64:
                 cache.pop(next(iter(cache)))
             cache[key] = (tuple(batch), out_shape)
-        return batch, out_shape
+        return BasicBatch(batch), out_shape
 
     def _batch_info(self, selection):
         md = self.metadata
@@ -269,6 +270,9 @@ class Array:
         """Plan a selection once; the returned program re-launches without re-planning."""
         import torch
 
+        if self._dispatch(selection) is not None:
+            raise NotImplementedError("prepare_read (and hipGraph capture) of an orthogonal, coordinate or mask "
+                                      "selection: only basic selections are planned ahead")
         batch, out_shape = self.batch_info(selection)
         if out is None:
             dev = device or getattr(self.store_path.store, "device", None) or torch.device("cuda:0")
@@ -277,7 +281,12 @@ class Array:
         return prog, out
 
     def get(self, selection=Ellipsis, out=None, device=None):
-        """Device-resident read: returns a torch tensor on the GPU."""
+        """Device-resident read: returns a torch tensor on the GPU (for
+        orthogonal, coordinate and mask selections too: dispatched as
+        __getitem__ does)."""
+        kind = self._dispatch(selection)
+        if kind is not None:
+            return self._get_fancy(self._indexer(kind, selection), out, device)
         batch, out_shape = self.batch_info(selection)
         import torch
 
@@ -299,6 +308,9 @@ class Array:
         (HipCodecPipeline._read_slabs); HBM-resident stores decode on the
         device and copy the result back once."""
         st = self.store_path.store
+        kind = self._dispatch(selection)
+        if kind is not None:
+            return self._get_fancy_host(self._indexer(kind, selection))
         if isinstance(st, DeviceStore):
             return buffer.to_numpy(self.get(selection), self.metadata.dtype)
         batch, out_shape = self.batch_info(selection)
@@ -316,6 +328,9 @@ class Array:
     def set(self, selection, value) -> None:
         """Array._set_selection (array.py:5563-5675): value may be a device
         tensor, a numpy array or a scalar."""
+        kind = self._dispatch(selection)
+        if kind is not None:
+            return self._set_fancy(self._indexer(kind, selection), value)
         batch, out_shape = self.batch_info(selection)
         if not batch:
             return
@@ -330,6 +345,147 @@ class Array:
 
     def __setitem__(self, selection, value) -> None:
         self.set(selection, value)
+
+    # ------------------------------- orthogonal, coordinate and mask selections
+    def _dispatch(self, selection):
+        """Array.__getitem__'s dispatch (array.py:2635-2641, indexing.py:270-331):
+        "vindex", "oindex", or None for a basic selection."""
+        if _selection_key(selection) is not None:
+            return None
+        nd = len(self.metadata.shape)
+        if is_pure_fancy_indexing(selection, nd):
+            return "vindex"
+        if is_pure_orthogonal_indexing(selection, nd):
+            return "oindex"
+        return None
+
+    def _indexer(self, kind: str, selection):
+        md = self.metadata
+        if not md.is_regular:
+            raise NotImplementedError("orthogonal, coordinate and mask selections of a rectilinear chunk grid")
+        if kind == "oindex":
+            return OrthogonalIndexer(selection, md.shape, md.chunk_shape)
+        sel = selection if isinstance(selection, tuple) else (selection,)
+        first = np.asarray(sel[0]) if isinstance(sel[0], list) else sel[0]
+        if len(sel) == 1 and is_bool_array(first) and first.shape == tuple(md.shape):
+            return MaskIndexer((first,), md.shape, md.chunk_shape)
+        return CoordinateIndexer(selection, md.shape, md.chunk_shape)
+
+    def _fancy_batch(self, indexer) -> list:
+        store, spec = self.store_path.store, self.spec
+        return [(StorePath(store, self._key(co)), spec, csel, osel, comp) for co, csel, osel, comp in indexer]
+
+    def _check_missing(self, batch, results) -> None:
+        if not self.config.read_missing_chunks:
+            for (bg, *_), r in zip(batch, results):
+                if r["status"] == "missing":
+                    raise ChunkNotFoundError(f"chunk {bg.path!r} is missing")
+
+    def _get_fancy(self, indexer, out=None, device=None):
+        import torch
+
+        if out is None:
+            dev = device or getattr(self.store_path.store, "device", None) or torch.device("cuda:0")
+            out = buffer.empty(indexer.shape, self.metadata.dtype, dev, self.config.order)
+        batch = self._fancy_batch(indexer)
+        if batch:
+            self._check_missing(batch, self.codec_pipeline.read_sync(batch, out, indexer.drop_axes))
+        return out.reshape(getattr(indexer, "sel_shape", tuple(out.shape)))
+
+    def _get_fancy_host(self, indexer) -> np.ndarray:
+        if isinstance(self.store_path.store, DeviceStore):
+            return buffer.to_numpy(self._get_fancy(indexer), self.metadata.dtype)
+        out = buffer.empty_pinned(indexer.shape, self.metadata.dtype, self.config.order)
+        batch = self._fancy_batch(indexer)
+        if batch:
+            self._check_missing(batch, self.codec_pipeline.read_sync(batch, out, indexer.drop_axes))
+        return out.reshape(getattr(indexer, "sel_shape", out.shape))
+
+    def _set_fancy(self, indexer, value) -> None:
+        import torch
+
+        flat = hasattr(indexer, "sel_shape")  # point lists: the value is taken flat (array.py:3596-3610)
+        if isinstance(value, torch.Tensor):
+            if flat and value.dim() > 0:
+                value = value.reshape(-1)
+            if value.dim() > 0 and tuple(value.shape) != tuple(indexer.shape):
+                value = value.broadcast_to(indexer.shape)
+        else:
+            a = np.asarray(value, dtype=self.metadata.dtype)
+            if flat and a.ndim > 0:
+                a = a.reshape(-1)
+            if a.shape not in ((), tuple(indexer.shape)):
+                a = np.broadcast_to(a, indexer.shape)
+            value = a
+        batch = self._fancy_batch(indexer)
+        if batch:
+            self.codec_pipeline.write_sync(batch, value, indexer.drop_axes)
+
+    def get_orthogonal_selection(self, selection, out=None):
+        """Array.get_orthogonal_selection: a host result (a device tensor: oindex
+        through get(), or pass a device `out`)."""
+        ix = OrthogonalIndexer(selection, self.metadata.shape, self._regular_chunks())
+        return self._get_fancy_host(ix) if out is None else self._get_fancy(ix, out)
+
+    def set_orthogonal_selection(self, selection, value) -> None:
+        self._set_fancy(OrthogonalIndexer(selection, self.metadata.shape, self._regular_chunks()), value)
+
+    def get_coordinate_selection(self, selection, out=None):
+        ix = CoordinateIndexer(selection, self.metadata.shape, self._regular_chunks())
+        return self._get_fancy_host(ix) if out is None else self._get_fancy(ix, out)
+
+    def set_coordinate_selection(self, selection, value) -> None:
+        self._set_fancy(CoordinateIndexer(selection, self.metadata.shape, self._regular_chunks()), value)
+
+    def get_mask_selection(self, mask, out=None):
+        ix = MaskIndexer(mask, self.metadata.shape, self._regular_chunks())
+        return self._get_fancy_host(ix) if out is None else self._get_fancy(ix, out)
+
+    def set_mask_selection(self, mask, value) -> None:
+        self._set_fancy(MaskIndexer(mask, self.metadata.shape, self._regular_chunks()), value)
+
+    def _regular_chunks(self):
+        if not self.metadata.is_regular:
+            raise NotImplementedError("orthogonal, coordinate and mask selections of a rectilinear chunk grid")
+        return self.metadata.chunk_shape
+
+    @property
+    def oindex(self) -> "_OIndex":
+        return _OIndex(self)
+
+    @property
+    def vindex(self) -> "_VIndex":
+        return _VIndex(self)
+
+
+class _OIndex:
+    """Array.oindex (indexing.py:999-1024)."""
+
+    def __init__(self, array: Array):
+        self.array = array
+
+    def __getitem__(self, selection):
+        return self.array.get_orthogonal_selection(selection)
+
+    def __setitem__(self, selection, value) -> None:
+        self.array.set_orthogonal_selection(selection, value)
+
+
+class _VIndex:
+    """Array.vindex (indexing.py:1376-1420): a Boolean mask of the array's
+    shape is a mask selection, anything else a coordinate selection."""
+
+    def __init__(self, array: Array):
+        self.array = array
+
+    def _indexer(self, selection):
+        return self.array._indexer("vindex", selection)
+
+    def __getitem__(self, selection):
+        return self.array._get_fancy_host(self._indexer(selection))
+
+    def __setitem__(self, selection, value) -> None:
+        self.array._set_fancy(self._indexer(selection), value)
 
 
 class ChunkNotFoundError(KeyError):

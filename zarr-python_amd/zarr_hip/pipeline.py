@@ -26,7 +26,7 @@ from typing import Any, Iterable
 import numpy as np
 
 from . import _native as N
-from . import staging
+from . import fancy, staging
 from .codecs import (ShardingCodec, TransposeCodec, evolve_codecs, is_v2_codec, parse_codecs, split_codecs,
                      split_host_tail)
 from .interop import device_tensor, host_array
@@ -1111,6 +1111,10 @@ class HipCodecPipeline:
         batch = normalize_batch(batch_info)
         if not batch:
             raise ValueError("empty batch")
+        if type(batch) is not BasicBatch and fancy.any_fancy(batch):
+            raise NotImplementedError("prepare_read (and hipGraph capture) of orthogonal, coordinate or mask "
+                                      "selections: read_sync serves them (fancy.py); only BasicIndexer "
+                                      "selections are planned ahead")
         if not isinstance(out, torch.Tensor) or not out.is_cuda:
             raise TypeError("HipCodecPipeline.read needs a device-resident out (torch CUDA tensor)")
         groups = spec_groups(batch)
@@ -1206,7 +1210,15 @@ class HipCodecPipeline:
         ``as_ndarray_like()`` is a ROCm tensor / DLPack capsule (decoded in
         place), or a host NDBuffer / numpy array: then the batch decodes into an
         HBM twin of `out` and the result is copied back (the regions no item
-        selects are carried through unchanged)."""
+        selects are carried through unchanged).
+
+        Items whose selections carry integer arrays or masks (zarr's orthogonal,
+        coordinate and mask indexers) take the gather route of fancy.py; the
+        basic items of such a batch still decode through the path below."""
+        if not isinstance(batch_info, list):
+            batch_info = list(batch_info)
+        if type(batch_info) is not BasicBatch and fancy.any_fancy(batch_info):
+            return fancy.read(self, batch_info, out, drop_axes)
         batch = normalize_batch(batch_info)
         if not batch:
             return ()
@@ -1442,6 +1454,10 @@ class HipCodecPipeline:
         from .writer import ChunkWriter
 
         torch = _torch()
+        if not isinstance(batch_info, list):
+            batch_info = list(batch_info)
+        if type(batch_info) is not BasicBatch and fancy.any_fancy(batch_info):  # orthogonal / coordinate / mask
+            return fancy.write(self, batch_info, value, drop_axes, partial_encode)
         batch = normalize_batch(batch_info)
         if not batch:
             return
@@ -1624,6 +1640,12 @@ class HipCodecPipeline:
         return await asyncio.to_thread(self.encode_sync, list(chunk_arrays_and_specs))
 
 
+class BasicBatch(list):
+    """A batch whose selections are known to be basic (Array.batch_info builds
+    them from BasicIndexer projections): read_sync / _write_sync skip the scan
+    for integer arrays and masks (fancy.any_fancy)."""
+
+
 def normalize_batch(batch_info: Iterable) -> list:
     """batch_info with every spec as this package's ArraySpec (zarr's ArraySpec
     carries a ZDType dtype, array_spec.py:137-186)."""
@@ -1649,7 +1671,9 @@ def _check_basic(selection) -> None:
     coordinate and mask indexers (OrthogonalIndexer, CoordinateIndexer,
     MaskIndexer: indexing.py:902-1046, 1171-1400) hand integer arrays or
     boolean masks; those are refused here, by name, instead of failing
-    somewhere in the planner."""
+    somewhere in the planner.  (read_sync / _write_sync route such items to
+    fancy.py before they normalise the batch; the batches that route builds
+    for this path are basic.)"""
     for s in selection:
         if not isinstance(s, (slice, int, np.integer)):
             raise NotImplementedError(
