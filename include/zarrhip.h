@@ -38,6 +38,11 @@
  *                     (chunk_utils.py:88-162) for the projections of
  *                     OrthogonalIndexer / CoordinateIndexer / MaskIndexer
  *                     (src/zarr/core/indexing.py:625-1046, 1171-1373).
+ *   zhip_points_count / zhip_points_fill
+ *                     CoordinateIndexer.__init__ (indexing.py:1171-1350) and
+ *                     MaskIndexer (:1353-1373) for coordinates that are device
+ *                     arrays: bounds, chunk of each point, grouping by chunk and
+ *                     the pair table zhip_select_copy reads, built on the device.
  *   zhip_plan_*       host-side constant tables (no reference counterpart:
  *                     the CRC-combine operators the GPU kernels need).
  *
@@ -570,10 +575,18 @@ typedef struct zhip_select_item {
  * (n_items + 1 words, the last = n_tiles; item i has
  * ceil(total_i / ZHIP_SELECT_TILE) tiles).  itemsize is 1, 2, 4 or 8; a and b
  * are aligned to it and do not overlap; a_size / b_size are the bytes readable
- * at a / writable at b.  THE CALLER VALIDATES THE TABLES (every offset inside
- * its buffer): the kernel only skips an element whose offsets fall outside
- * a_size / b_size, as a second fence.  Asynchronous on `stream`; afterwards
- * zhip_last_kernel() is "k_select_copy". */
+ * at a / writable at b.  THE TABLES ARE VALIDATED BEFORE THE LAUNCH (every
+ * offset inside its buffer), by whoever builds them.  A table built on the
+ * host is checked by the caller.  A table built by zhip_points_fill (below) is
+ * valid by construction, given a geometry the caller has checked against its
+ * buffers: every slot-side entry lies inside one chunk-shaped slot, because
+ * the same function that produced the offset range-checked the coordinates it
+ * came from (a point that fails the check writes no pair), and every entry of
+ * the other side is k * pair_stride with k < n; with the item's base that is
+ * inside the scratch and inside out / value when slot bases + slot bytes and
+ * (n - 1) * pair_stride + itemsize are.  Either way the kernel only skips an
+ * element whose offsets fall outside a_size / b_size, as a second fence.
+ * Asynchronous on `stream`; afterwards zhip_last_kernel() is "k_select_copy". */
 int zhip_select_copy(const zhip_select_item *d_items, uint32_t n_items, const int64_t *d_table,
                      const uint32_t *d_tile_prefix, uint32_t n_tiles, const void *a, uint64_t a_size,
                      void *b, uint64_t b_size, uint32_t itemsize, void *stream);
@@ -585,6 +598,78 @@ int zhip_select_copy(const zhip_select_item *d_items, uint32_t n_items, const in
 int zhip_emulate_select_copy(const zhip_select_item *items, uint32_t n_items, const int64_t *table,
                              uint64_t table_pairs, const uint32_t *tile_prefix, uint32_t n_tiles,
                              const void *a, uint64_t a_size, void *b, uint64_t b_size, uint32_t itemsize);
+
+/* ---- device-built point tables (coordinate and mask selections) ----
+ *
+ * For a coordinate or mask selection whose coordinates are already on the
+ * device, these build the grouped (A, B) pair table zhip_select_copy consumes
+ * without a host pass over the points.  They replace, per point,
+ * CoordinateIndexer.__init__ (src/zarr/core/indexing.py:1171-1350: wraparound,
+ * bounds check, the chunk of each point, the argsort that groups points by
+ * chunk, the per-chunk slices) and, fed with a mask's nonzero coordinates,
+ * MaskIndexer (indexing.py:1353-1373); and the host build of the pair table.
+ *
+ *   zhip_points_count   counts[rix] = points of the chunk with row-major grid
+ *                       index rix; *d_err |= 1 << d for every dimension d with
+ *                       an index outside [-shape[d], shape[d]) (such a point is
+ *                       not counted).  The host reads counts and the error
+ *                       word back once, raises or computes first[rix] (the
+ *                       exclusive prefix sum of counts) and builds one
+ *                       zhip_select_item per touched chunk: a single table
+ *                       dimension, count = total = counts[rix], table_off =
+ *                       first[rix], the slot-side base = the chunk's slot.
+ *   zhip_points_fill    writes the pair of every in-range point k at
+ *                       table[first[rix] + p], p a distinct position in
+ *                       [0, counts[rix]) (the order inside a chunk's range is
+ *                       unspecified: every pair carries its own offsets).
+ *                       Read (write = 0): A = the element's byte offset inside
+ *                       a C-order chunk-shaped slot (slot_stride), B = k *
+ *                       pair_stride.  Write (write = 1): A = k * pair_stride
+ *                       (0 for a scalar value), B = the slot offset.
+ *
+ * Limits, checked by both entry points (ZHIP_E_UNSUPPORTED past them; the
+ * Python caller tests them before any launch and serves such a selection with
+ * host indices): */
+#define ZHIP_POINTS_MAX_N 0x7fffffffu       /* points of one selection: n < 2^31           */
+#define ZHIP_POINTS_MAX_DIM 0x7fffffffu     /* every array dimension < 2^31                */
+#define ZHIP_POINTS_MAX_GRID (1u << 22)     /* chunks of the grid (entries of counts)      */
+#define ZHIP_POINTS_LDS_BINS 4096u          /* grids up to this size: per-workgroup LDS
+                                               histogram, one global atomic per non-empty
+                                               bin; larger grids: one global atomic per point */
+#define ZHIP_POINTS_RUN 2048u               /* points of one workgroup (256 lanes x 8)     */
+
+typedef struct zhip_points_geom {
+    int32_t ndim;                        /* 1 .. ZHIP_MAX_DIMS                              */
+    uint32_t write;                      /* pair order: 0 read, 1 write                     */
+    int64_t pair_stride;                 /* bytes per point on the out (read) / value (write) side */
+    uint32_t shape[ZHIP_MAX_DIMS];       /* array length                                    */
+    uint32_t chunk[ZHIP_MAX_DIMS];       /* chunk length (>= 1)                             */
+    zhip_fdiv div[ZHIP_MAX_DIMS];        /* division by chunk                               */
+    uint32_t grid[ZHIP_MAX_DIMS];        /* chunks along the dimension: ceil(shape / chunk) */
+    int64_t slot_stride[ZHIP_MAX_DIMS];  /* byte stride of the dimension inside a slot      */
+} zhip_points_geom;                      /* 240 bytes */
+
+/* d_coords: a HOST array of geom->ndim device pointers, each to n contiguous
+ * int64 coordinates (8-byte aligned).  d_counts: prod(grid) zeroed words;
+ * d_err: one zeroed word.  n = 0 launches nothing.  Asynchronous on `stream`;
+ * afterwards zhip_last_kernel() is "k_points_count". */
+int zhip_points_count(const zhip_points_geom *geom, const int64_t *const *d_coords, uint64_t n,
+                      uint32_t *d_counts, uint32_t *d_err, void *stream);
+/* d_first: prod(grid) words, the exclusive prefix sum of zhip_points_count's
+ * counts for the same coordinates; d_cursor: prod(grid) zeroed words (each
+ * ends equal to its count); d_table: n pairs (2 n int64), 16-byte aligned.  A
+ * pair whose index would be n or more is not written.  Afterwards
+ * zhip_last_kernel() is "k_points_fill". */
+int zhip_points_fill(const zhip_points_geom *geom, const int64_t *const *d_coords, uint64_t n,
+                     const uint32_t *d_first, uint32_t *d_cursor, int64_t *d_table, void *stream);
+/* CPU-only test hook: both steps over host memory with the kernels' located-
+ * point function (one shared host/device function).  Zeroes counts / cursor /
+ * *err, counts; with *err != 0 stops there (first, cursor and table
+ * untouched), else writes first (the exclusive prefix sum) and fills the
+ * table in point order.  counts / first / cursor: prod(grid) words; table: n
+ * pairs. */
+int zhip_emulate_points(const zhip_points_geom *geom, const int64_t *const *coords, uint64_t n,
+                        uint32_t *counts, uint32_t *err, uint32_t *first, uint32_t *cursor, int64_t *table);
 
 /* Host CRC-32C (reflected 0x82F63B78, init / xorout 0xFFFFFFFF) of nbytes at
  * data: the host stage of a chain, where the bytes never reach the GPU -- a

@@ -4,8 +4,12 @@
 A 256^3 float32 array in 64^3 chunks (bytes + crc32c), device-resident store:
   (i)  oindex with a full-length permuted index on dimension 0 (dense: 2^24
        elements, affine inner dimensions);
-  (ii) vindex of 10^6 random points.
-For each: Array.get(...) end to end (host clock around a call that ends in a
+  (ii) vindex of 10^6 random points;
+  (iii) the same points as device tensors, planned on the device
+       (zarr_hip.points): Array.get end to end, the device-event time of
+       count + fill + gather, and the host clock of the planning at a tenth of
+       the points and at all of them.
+For (i) and (ii): Array.get(...) end to end (host clock around a call that ends in a
 device synchronise), and the gather launch alone (device events around
 SelectTables.launch: the table upload and k_select_copy) with its bytes per
 second.  Next to them, on the same build: the basic full read arr.get(...),
@@ -16,7 +20,8 @@ numpy fancy indexing.
 
 --profile runs each gather a few times and nothing else, for
 `rocprofv3 --kernel-trace --stats -- python scripts/fancy_bench.py --profile`
-(k_select_copy's own time).  Prints one JSON line.
+(k_select_copy's, k_points_count's and k_points_fill's own times).  Prints one
+JSON line.
 """
 
 import argparse
@@ -126,6 +131,54 @@ def main():
                      "gather_GBps": moved / ms / 1e6, "table_bytes": table_bytes,
                      "get_ms_median": e2e[0], "get_ms_min": e2e[1]}
         del keep
+    # (iii) the points of (ii) as device tensors: planned on the device (zarr_hip.points)
+    from zarr_hip.points import DeviceCoordinateIndexer
+
+    isz = 4
+    cstr = [c * c * isz, c * isz, isz]
+    slot_bytes = c * c * c * isz
+
+    def device_plan_and_gather(dsel, out):
+        """count (+ the one readback) + fill + gather against the decoded scratch."""
+        ix = DeviceCoordinateIndexer(dsel, shape, chunks)
+        table = ix.build_table(cstr, isz, False)
+        tabs = fancy.SelectTables(isz, fancy.tensor_extent(scratch), fancy.tensor_extent(out))
+        for k, rix in enumerate(ix.chunk_rixs):
+            tabs.add_points(int(ix.counts[k]), int(ix.first[k]), int(rix) * slot_bytes, slot_bytes, (ix.n - 1) * isz)
+        return tabs.launch(scratch, out, dev, table=table), table
+
+    dpts = tuple(torch.from_numpy(p).to(dev) for p in pts)
+    got = arr.get(dpts)
+    if not got.is_cuda or buffer.to_numpy(got, np.float32).tobytes() != np.ascontiguousarray(want["vindex_points"]).tobytes():
+        raise SystemExit("fancy_bench: vindex_points_device differs from numpy")
+    out = torch.empty(args.points, dtype=torch.float32, device=dev)
+    keep = device_plan_and_gather(dpts, out)
+    sync()
+    if buffer.to_numpy(out, np.float32).tobytes() != np.ascontiguousarray(want["vindex_points"]).tobytes():
+        raise SystemExit("fancy_bench: vindex_points_device: the timed plan + gather differs from numpy")
+    if args.profile:
+        for _ in range(5):
+            keep = device_plan_and_gather(dpts, out)
+        sync()
+    else:
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for a, b in ev:
+            a.record()
+            keep = device_plan_and_gather(dpts, out)
+            b.record()
+        sync()
+        e2e = wall(lambda: arr.get(dpts), args.reps)
+        r3 = {"elements": args.points, "get_ms_median": e2e[0], "get_ms_min": e2e[1],
+              "count_fill_gather_event_ms": float(np.median([a.elapsed_time(b) for a, b in ev]))}
+        # the host section against the point count: planning (count launch, the readback, the items) on the host
+        # clock, for a tenth of the points and for all of them -- per-point host work would show as a tenfold step
+        for frac in (10, 1):
+            sub = tuple(t[: args.points // frac].contiguous() for t in dpts)
+            sub_out = out[: args.points // frac]
+            p = wall(lambda: device_plan_and_gather(sub, sub_out), args.reps)
+            r3[f"plan_and_gather_wall_ms_{args.points // frac}_points"] = {"median": p[0], "min": p[1]}
+        res["vindex_points_device"] = r3
+    del keep
     if not args.profile:
         b = wall(lambda: arr.get((Ellipsis,)), args.reps)
         res["basic_full_get_ms"] = {"median": b[0], "min": b[1]}

@@ -16,6 +16,7 @@
 #include "../../include/zarrhip.h"
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
+#include "zhip_points.h"
 #include "zhip_select.h"
 
 using namespace zhip;
@@ -1516,6 +1517,96 @@ int zhip_emulate_select_copy(const zhip_select_item* items, uint32_t n_items, co
                     return set_err(ZHIP_E_BOUNDS, "element offset outside its buffer");
                 memcpy((uint8_t*)b + bo, (const uint8_t*)a + ao, itemsize);
             }
+    }
+    return ZHIP_OK;
+}
+
+// ---- zhip_points_count / zhip_points_fill: device-built point tables (points.hip) ----
+// The geometry a caller could get wrong, the limits, and the grid size.
+static int points_args(const zhip_points_geom* g, const void* const* coords, uint64_t n, uint64_t* n_chunks) {
+    if (!g || !coords) return set_err(ZHIP_E_INVALID, "null argument");
+    if (g->ndim < 1 || g->ndim > ZHIP_MAX_DIMS) return set_err(ZHIP_E_INVALID, "points geometry ndim");
+    if (g->write > 1) return set_err(ZHIP_E_INVALID, "points geometry write flag");
+    if (n > ZHIP_POINTS_MAX_N) return set_err(ZHIP_E_UNSUPPORTED, "2^31 or more points in one selection");
+    for (int d = 0; d < g->ndim; ++d) {
+        if (g->shape[d] > ZHIP_POINTS_MAX_DIM) return set_err(ZHIP_E_UNSUPPORTED, "an array dimension of 2^31 or more");
+        if (g->chunk[d] < 1 || g->chunk[d] > ZHIP_POINTS_MAX_DIM) return set_err(ZHIP_E_INVALID, "points geometry chunk length");
+        const zhip_fdiv f = make_fdiv(g->chunk[d]);
+        if (f.m != g->div[d].m || f.s != g->div[d].s) return set_err(ZHIP_E_INVALID, "points geometry divisor");
+        if (g->grid[d] != (uint32_t)(((uint64_t)g->shape[d] + g->chunk[d] - 1) / g->chunk[d]))
+            return set_err(ZHIP_E_INVALID, "points geometry grid length");
+        if (n && (!coords[d] || ((uintptr_t)coords[d] & 7))) return set_err(ZHIP_E_INVALID, "coordinate array null or unaligned");
+    }
+    *n_chunks = points_grid_size(*g);
+    if (!*n_chunks) return set_err(ZHIP_E_UNSUPPORTED, "chunk grid larger than ZHIP_POINTS_MAX_GRID");
+    return ZHIP_OK;
+}
+
+static PointsCoords points_coords(const zhip_points_geom* g, const int64_t* const* coords) {
+    PointsCoords pc;
+    for (int d = 0; d < ZHIP_MAX_DIMS; ++d) pc.c[d] = d < g->ndim ? coords[d] : nullptr;
+    return pc;
+}
+
+int zhip_points_count(const zhip_points_geom* geom, const int64_t* const* d_coords, uint64_t n, uint32_t* d_counts,
+                      uint32_t* d_err, void* stream) {
+    uint64_t n_chunks = 0;
+    const int rc = points_args(geom, (const void* const*)d_coords, n, &n_chunks);
+    if (rc != ZHIP_OK) return rc;
+    if (!d_counts || !d_err) return set_err(ZHIP_E_INVALID, "null argument");
+    if (n == 0) return ZHIP_OK;
+    const int e = points_count_launch(*geom, points_coords(geom, d_coords), (uint32_t)n, (uint32_t)n_chunks, d_counts,
+                                      d_err, stream);
+    if (e != 0) return set_err(ZHIP_E_HIP, std::string("k_points_count launch: ") + hipGetErrorString((hipError_t)e));
+    return ZHIP_OK;
+}
+
+int zhip_points_fill(const zhip_points_geom* geom, const int64_t* const* d_coords, uint64_t n, const uint32_t* d_first,
+                     uint32_t* d_cursor, int64_t* d_table, void* stream) {
+    uint64_t n_chunks = 0;
+    const int rc = points_args(geom, (const void* const*)d_coords, n, &n_chunks);
+    if (rc != ZHIP_OK) return rc;
+    if (!d_first || !d_cursor || !d_table) return set_err(ZHIP_E_INVALID, "null argument");
+    if ((uintptr_t)d_table & 15) return set_err(ZHIP_E_INVALID, "pair table not 16-byte aligned");
+    if (n == 0) return ZHIP_OK;
+    const int e = points_fill_launch(*geom, points_coords(geom, d_coords), (uint32_t)n, (uint32_t)n_chunks, d_first,
+                                     d_cursor, d_table, stream);
+    if (e != 0) return set_err(ZHIP_E_HIP, std::string("k_points_fill launch: ") + hipGetErrorString((hipError_t)e));
+    return ZHIP_OK;
+}
+
+// Both steps on the host, in point order, with the kernels' points_locate /
+// points_pair: count, then (no index out of range) the prefix sum and the fill.
+int zhip_emulate_points(const zhip_points_geom* geom, const int64_t* const* coords, uint64_t n, uint32_t* counts,
+                        uint32_t* err, uint32_t* first, uint32_t* cursor, int64_t* table) {
+    uint64_t n_chunks = 0;
+    const int rc = points_args(geom, (const void* const*)coords, n, &n_chunks);
+    if (rc != ZHIP_OK) return rc;
+    if (!counts || !err || !first || !cursor || (n && !table)) return set_err(ZHIP_E_INVALID, "null argument");
+    const zhip_points_geom& g = *geom;
+    memset(counts, 0, n_chunks * sizeof(uint32_t));
+    memset(cursor, 0, n_chunks * sizeof(uint32_t));
+    *err = 0;
+    int64_t x[ZHIP_MAX_DIMS] = {0};
+    uint32_t rix;
+    int64_t off;
+    for (uint64_t k = 0; k < n; ++k) {
+        for (int d = 0; d < g.ndim; ++d) x[d] = coords[d][k];
+        const uint32_t e = points_locate(g, x, rix, off);
+        if (e) *err |= e; else counts[rix] += 1;
+    }
+    if (*err) return ZHIP_OK;
+    uint32_t at = 0;
+    for (uint64_t b = 0; b < n_chunks; ++b) {
+        first[b] = at;
+        at += counts[b];
+    }
+    for (uint64_t k = 0; k < n; ++k) {
+        for (int d = 0; d < g.ndim; ++d) x[d] = coords[d][k];
+        if (points_locate(g, x, rix, off)) continue;
+        const uint64_t p = (uint64_t)first[rix] + cursor[rix]++;
+        if (p >= n) return set_err(ZHIP_E_BOUNDS, "pair index outside the table");
+        points_pair(g, k, off, table[2 * p], table[2 * p + 1]);
     }
     return ZHIP_OK;
 }

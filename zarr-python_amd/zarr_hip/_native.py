@@ -173,6 +173,17 @@ SELECT_ITEM_DT = np.dtype([("a_base", "<i8"), ("b_base", "<i8"), ("ndim", "<u4")
                            ("_pad", "<u4", (2,)), ("dims", SELECT_DIM_DT, (MAX_DIMS,))])
 assert SELECT_DIM_DT.itemsize == 64 and SELECT_ITEM_DT.itemsize == 544
 
+# zhip_points_geom and the limits of zhip_points_count / zhip_points_fill (include/zarrhip.h)
+POINTS_MAX_N = 0x7FFFFFFF
+POINTS_MAX_DIM = 0x7FFFFFFF
+POINTS_MAX_GRID = 1 << 22
+POINTS_LDS_BINS = 4096
+POINTS_RUN = 2048
+POINTS_GEOM_DT = np.dtype([("ndim", "<i4"), ("write", "<u4"), ("pair_stride", "<i8"), ("shape", "<u4", (MAX_DIMS,)),
+                           ("chunk", "<u4", (MAX_DIMS,)), ("div", "<u4", (MAX_DIMS, 2)), ("grid", "<u4", (MAX_DIMS,)),
+                           ("slot_stride", "<i8", (MAX_DIMS,))])
+assert POINTS_GEOM_DT.itemsize == 240
+
 
 class NativeError(RuntimeError):
     pass
@@ -290,6 +301,12 @@ def lib():
     L.zhip_select_copy.restype = ctypes.c_int
     L.zhip_emulate_select_copy.argtypes = [vp, u32, vp, u64, vp, u32, vp, u64, vp, u64, u32]
     L.zhip_emulate_select_copy.restype = ctypes.c_int
+    L.zhip_points_count.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.zhip_points_count.restype = ctypes.c_int
+    L.zhip_points_fill.argtypes = [vp, vp, u64, vp, vp, vp, vp]
+    L.zhip_points_fill.restype = ctypes.c_int
+    L.zhip_emulate_points.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp]
+    L.zhip_emulate_points.restype = ctypes.c_int
     if L.zhip_abi_version() != 1:
         raise NativeError("libzarrhip ABI version mismatch")
     if L.zhip_tuning_build() and not _override_allowed():

@@ -18,7 +18,7 @@ from typing import Any
 
 import numpy as np
 
-from . import buffer
+from . import buffer, points
 from .codecs import BytesCodec, Crc32cCodec, ShardingCodec, parse_codecs
 from .grid import ChunkGrid
 from .indexing import (CoordinateIndexer, MaskIndexer, OrthogonalIndexer, basic_projections, chunk_batch,
@@ -309,6 +309,8 @@ class Array:
         device and copy the result back once."""
         st = self.store_path.store
         kind = self._dispatch(selection)
+        if kind == "device":  # indices on the device: planned there; the result is still a host array
+            return buffer.to_numpy(self._get_fancy(self._indexer(kind, selection)), self.metadata.dtype)
         if kind is not None:
             return self._get_fancy_host(self._indexer(kind, selection))
         if isinstance(st, DeviceStore):
@@ -349,9 +351,12 @@ class Array:
     # ------------------------------- orthogonal, coordinate and mask selections
     def _dispatch(self, selection):
         """Array.__getitem__'s dispatch (array.py:2635-2641, indexing.py:270-331):
-        "vindex", "oindex", or None for a basic selection."""
+        "vindex", "oindex", or None for a basic selection; "device" for a
+        selection that holds device tensors (points.py)."""
         if _selection_key(selection) is not None:
             return None
+        if points.has_device_index(selection):
+            return "device"
         nd = len(self.metadata.shape)
         if is_pure_fancy_indexing(selection, nd):
             return "vindex"
@@ -363,6 +368,8 @@ class Array:
         md = self.metadata
         if not md.is_regular:
             raise NotImplementedError("orthogonal, coordinate and mask selections of a rectilinear chunk grid")
+        if kind == "device":
+            return self._device_indexer(selection)
         if kind == "oindex":
             return OrthogonalIndexer(selection, md.shape, md.chunk_shape)
         sel = selection if isinstance(selection, tuple) else (selection,)
@@ -381,9 +388,112 @@ class Array:
                 if r["status"] == "missing":
                     raise ChunkNotFoundError(f"chunk {bg.path!r} is missing")
 
+    # --- coordinate and mask selections whose indices are device tensors (points.py)
+    def _device_indexer(self, selection, mask: bool | None = None):
+        """DeviceMaskIndexer for a Boolean device tensor (vindex's rule: of the
+        array's shape), else DeviceCoordinateIndexer.  Past the device route's
+        limits: the host indexer over a host copy of the indices."""
+        import torch
+
+        md = self.metadata
+        chunks = self._regular_chunks()
+        points.check_unmixed(selection)
+        sel = selection if isinstance(selection, tuple) else (selection,)
+        if mask is None:
+            mask = (len(sel) == 1 and isinstance(sel[0], torch.Tensor) and sel[0].dtype == torch.bool
+                    and tuple(sel[0].shape) == tuple(md.shape))
+        try:
+            return (points.DeviceMaskIndexer if mask else points.DeviceCoordinateIndexer)(selection, md.shape, chunks)
+        except points.PointsLimit:
+            host = points.to_host(selection)
+            return (MaskIndexer if mask else CoordinateIndexer)(host, md.shape, chunks)
+
+    def _points_getters(self, ix) -> list:
+        store = self.store_path.store
+        return [StorePath(store, self._key(co)) for co in ix.chunk_coords()]
+
+    def _run_device(self, ix, device=None):
+        """The device a selection with device indices runs on: the indices'.
+        A store or a caller that names another one raises."""
+        import torch
+
+        def index(d):
+            d = torch.device(d)
+            return torch.cuda.current_device() if d.index is None else d.index
+
+        for what, d in (("device argument", device), ("store", getattr(self.store_path.store, "device", None))):
+            if d is not None and (torch.device(d).type != "cuda" or index(d) != index(ix.device)):
+                raise ValueError(f"the selection's indices are on {ix.device}, the {what} is on {d}: the indices "
+                                 "of a device-planned selection live on the device the array is read on")
+        return ix.device
+
+    def _get_points(self, ix, out=None, device=None):
+        """A device tensor reshaped to sel_shape; with `out` (a device tensor or
+        a host array of the selection's size): out, filled."""
+        from .interop import device_tensor, host_array
+
+        dev = self._run_device(ix, device)
+        dt = self.metadata.dtype
+        target = None
+        if out is not None:
+            target = device_tensor(out)
+            if target is None:
+                target = host_array(out)
+                if target is None:
+                    raise TypeError(f"cannot decode into a {type(out).__name__}")
+            size = target.numel() if hasattr(target, "numel") else target.size
+            if size != ix.n:
+                raise ValueError(f"out holds {size} elements, the selection {ix.n}")
+        flat = None
+        if target is not None and hasattr(target, "numel") and target.device == dev:
+            try:
+                flat = target.view(-1)  # decoded in place
+            except RuntimeError:
+                flat = None
+        direct = flat is not None
+        if flat is None:
+            flat = buffer.empty((ix.n,), dt, dev)
+        getters = self._points_getters(ix)
+        if getters:
+            from . import fancy
+
+            results = fancy.read_points(self.codec_pipeline, getters, self.spec, ix, flat)
+            self._check_missing([(g,) for g in getters], results)
+        if target is None:
+            return flat.reshape(ix.sel_shape)
+        if not direct:
+            if hasattr(target, "numel"):
+                target.copy_(flat.reshape(target.shape))
+            else:
+                buffer.copy_to_host(flat.reshape(target.shape), target)
+        return out
+
+    def _set_points(self, ix, value) -> None:
+        import torch
+
+        from . import fancy
+
+        self._run_device(ix)
+        if isinstance(value, torch.Tensor):
+            if value.numel() == 1:
+                value = value.reshape(())
+            elif value.numel() != ix.n:
+                raise ValueError(f"value of {value.numel()} elements for a selection of {ix.n} points")
+            else:
+                value = value.reshape(-1)  # point lists: the value is taken flat
+        else:
+            a = np.asarray(value, dtype=self.metadata.dtype)
+            value = a.reshape(()) if a.size == 1 else np.broadcast_to(a.reshape(-1), (ix.n,))
+        getters = self._points_getters(ix)
+        if getters:
+            fancy.write_points(self.codec_pipeline, getters, self.spec, ix, value,
+                               distinct=isinstance(ix, points.DeviceMaskIndexer))
+
     def _get_fancy(self, indexer, out=None, device=None):
         import torch
 
+        if isinstance(indexer, points.DeviceCoordinateIndexer):
+            return self._get_points(indexer, out, device)
         if out is None:
             dev = device or getattr(self.store_path.store, "device", None) or torch.device("cuda:0")
             out = buffer.empty(indexer.shape, self.metadata.dtype, dev, self.config.order)
@@ -404,6 +514,8 @@ class Array:
     def _set_fancy(self, indexer, value) -> None:
         import torch
 
+        if isinstance(indexer, points.DeviceCoordinateIndexer):
+            return self._set_points(indexer, value)
         flat = hasattr(indexer, "sel_shape")  # point lists: the value is taken flat (array.py:3596-3610)
         if isinstance(value, torch.Tensor):
             if flat and value.dim() > 0:
@@ -431,17 +543,27 @@ class Array:
         self._set_fancy(OrthogonalIndexer(selection, self.metadata.shape, self._regular_chunks()), value)
 
     def get_coordinate_selection(self, selection, out=None):
+        """Coordinates given as device tensors are planned on the device and
+        give a device tensor (points.py); host coordinates a host result."""
+        if points.has_device_index(selection):
+            return self._get_fancy(self._device_indexer(selection, mask=False), out)
         ix = CoordinateIndexer(selection, self.metadata.shape, self._regular_chunks())
         return self._get_fancy_host(ix) if out is None else self._get_fancy(ix, out)
 
     def set_coordinate_selection(self, selection, value) -> None:
+        if points.has_device_index(selection):
+            return self._set_fancy(self._device_indexer(selection, mask=False), value)
         self._set_fancy(CoordinateIndexer(selection, self.metadata.shape, self._regular_chunks()), value)
 
     def get_mask_selection(self, mask, out=None):
+        if points.has_device_index(mask):
+            return self._get_fancy(self._device_indexer(mask, mask=True), out)
         ix = MaskIndexer(mask, self.metadata.shape, self._regular_chunks())
         return self._get_fancy_host(ix) if out is None else self._get_fancy(ix, out)
 
     def set_mask_selection(self, mask, value) -> None:
+        if points.has_device_index(mask):
+            return self._set_fancy(self._device_indexer(mask, mask=True), value)
         self._set_fancy(MaskIndexer(mask, self.metadata.shape, self._regular_chunks()), value)
 
     def _regular_chunks(self):
@@ -479,9 +601,11 @@ class _VIndex:
         self.array = array
 
     def _indexer(self, selection):
-        return self.array._indexer("vindex", selection)
+        return self.array._indexer("device" if points.has_device_index(selection) else "vindex", selection)
 
     def __getitem__(self, selection):
+        if points.has_device_index(selection):  # device indices give a device tensor
+            return self.array._get_fancy(self._indexer(selection))
         return self.array._get_fancy_host(self._indexer(selection))
 
     def __setitem__(self, selection, value) -> None:

@@ -26,6 +26,10 @@ device, so all but the LAST occurrence (in table order) are dropped on the
 host: per dimension for orthogonal forms, by flat chunk index for point
 lists.  The reference's own order within a chunk is unspecified: the argsort
 that groups indices by chunk is not stable (indexing.py:803, 1299).
+
+Coordinate and mask selections whose indices are device tensors skip the host
+normaliser: read_points / write_points run the same slots, scratch budget and
+routes over a pair table that k_points_fill built on the device (points.py).
 """
 
 from __future__ import annotations
@@ -401,6 +405,33 @@ class SelectTables:
         rec["total"] = nz.total
         self.items.append(rec)
 
+    def add_points(self, count: int, table_off: int, slot_base: int, slot_bytes: int, lin_last: int,
+                   write: bool = False) -> None:
+        """One touched chunk of a device-built point table (zhip_points_fill):
+        a single table dimension over pairs [table_off, table_off + count) of
+        the DEVICE table given to launch().  The slot-side entries lie in
+        [0, slot_bytes) by construction and the other side's are at most
+        lin_last (zarrhip.h), so the check is of the two ends."""
+        if count == 0:
+            return
+        za, zb = (1, 0) if write else (0, 1)
+        lo = [int(slot_base), 0]
+        hi = [int(slot_base) + int(slot_bytes) - self.itemsize, int(lin_last)]
+        for z, size, name in ((za, self.a_size, "source"), (zb, self.b_size, "destination")):
+            if lo[z] < 0 or hi[z] + self.itemsize > size:
+                raise IndexError(f"selection reaches outside its {name} buffer (bytes {lo[z]} .. "
+                                 f"{hi[z] + self.itemsize} of {size})")
+        rec = np.zeros((), N.SELECT_ITEM_DT)
+        D = rec["dims"][0]
+        D["count"] = count
+        D["div"] = N.fdiv(count)
+        D["table"] = 1
+        D["table_off"] = table_off
+        rec["a_base"], rec["b_base"] = lo[za], lo[zb]
+        rec["ndim"] = 1
+        rec["total"] = count
+        self.items.append(rec)
+
     def finish(self):
         """(items, table pairs, tile prefix, n_tiles) as contiguous arrays."""
         items = np.array(self.items, N.SELECT_ITEM_DT) if self.items else np.zeros(0, N.SELECT_ITEM_DT)
@@ -422,20 +453,28 @@ class SelectTables:
             items.ctypes.data, len(items), table.ctypes.data, len(table), prefix.ctypes.data, n_tiles,
             a.ctypes.data, self.a_size, b.ctypes.data, self.b_size, self.itemsize), "zhip_emulate_select_copy")
 
-    def launch(self, a, b, device):
+    def launch(self, a, b, device, table=None):
         """One k_select_copy launch on torch's current stream of `device`:
-        a, b are device tensors whose extents are a_size / b_size.  Returns
-        the uploaded table block (keep it until the stream has passed)."""
+        a, b are device tensors whose extents are a_size / b_size.  table: a
+        device-resident pair table (an int64 tensor, add_points' items index
+        it): only items and prefix are uploaded then.  Returns the uploaded
+        table block (keep it until the stream has passed)."""
         from .pipeline import _stream_handle, _Upload
 
-        items, table, prefix, n_tiles = self.finish()
+        items, host_table, prefix, n_tiles = self.finish()
         if n_tiles == 0:
             return None
+        if table is not None and self.tables:
+            raise ValueError("host-built table dimensions next to a device-resident table")
         stream = _stream_handle(device)
         up = _Upload(device)
-        for part in (items, table, prefix):
+        for part in (items, prefix) if table is not None else (items, host_table, prefix):
             up.add(part.view(np.uint8).reshape(-1))
-        p_items, p_table, p_prefix = up.commit(stream)
+        if table is not None:
+            p_items, p_prefix = up.commit(stream)
+            p_table = table.data_ptr()
+        else:
+            p_items, p_table, p_prefix = up.commit(stream)
         N.check(N.lib().zhip_select_copy(p_items, len(items), p_table, p_prefix, n_tiles, a.data_ptr(), self.a_size,
                                          b.data_ptr(), self.b_size, self.itemsize, stream), "zhip_select_copy")
         return up.dev
@@ -644,3 +683,137 @@ def write(pipe, items, value, drop_axes, partial_encode: bool) -> None:
             pipe._write_sync(wbatch, scratch, (), partial_encode)
         if basic:
             pipe._write_sync([batch[i] for i in basic], value, drop_axes, partial_encode)
+
+
+# ---------------------------------------------- device-planned point lists
+def _points_setup(pipe, spec, ix, n_getters: int):
+    if spec.ndim == 0:
+        raise NotImplementedError("a non-basic selection of a 0-dimensional chunk")
+    if tuple(int(s) for s in spec.shape) != tuple(ix.chunk_shape):
+        raise ValueError("the indexer's chunk shape is not the spec's")
+    if n_getters != len(ix.chunk_rixs):
+        raise ValueError(f"{n_getters} byte getters for {len(ix.chunk_rixs)} touched chunks")
+    whole = [(0, int(s)) for s in spec.shape]
+    return whole, tuple(slice(0, int(s)) for s in spec.shape)
+
+
+def read_points(pipe, getters, spec, ix, dev_out) -> tuple:
+    """A coordinate or mask read planned on the device (points.py): getters[i]
+    is the chunk ix.chunk_rixs[i]; dev_out a 1-d device tensor of ix.n
+    elements (any stride) on the indexer's device.  Each touched chunk is one
+    item whose box is the WHOLE chunk (the whole shard of a sharded chain:
+    narrowing it would need per-axis minima from the device), decoded into
+    its slot; the selection's pair table is built once by k_points_fill, the
+    sub-batches differ only in their items.  Slots, scratch budget, the direct
+    and composed routes and the single result readback are read()'s."""
+    from .buffer import torch_dtype
+    from .pipeline import ProgramGroup, _torch
+
+    torch = _torch()
+    whole, csel = _points_setup(pipe, spec, ix, len(getters))
+    device = dev_out.device
+    if device != ix.device:
+        raise ValueError(f"the coordinates are on {ix.device}, the read runs on {device}")
+    itemsize = dev_out.element_size()
+    if np.dtype(spec.dtype).itemsize != itemsize:
+        raise TypeError("out dtype itemsize does not match the array dtype")
+    n = ix.n
+    if dev_out.dim() != 1 or dev_out.numel() != n:
+        raise ValueError(f"out of shape {tuple(dev_out.shape)} for a selection of {n} points")
+    if n == 0:
+        return ()
+    ostride = int(dev_out.stride(0)) * itemsize
+    results: list = [None] * len(getters)
+    direct = _direct(pipe)
+    s0 = spec.shape[0]
+    cstr = _scratch_strides(spec, itemsize)
+    slot_bytes = cstr[0] * s0
+    per = _slots(spec, len(getters))
+    progs, groups, keep = [], [], []
+    with torch.cuda.device(device):
+        scratch = torch.empty((per * s0,) + tuple(spec.shape[1:]), dtype=torch_dtype(spec.dtype), device=device)
+        table = ix.build_table(cstr, ostride, False)
+        for at in range(0, len(getters), per):
+            idx = list(range(at, min(at + per, len(getters))))
+            tabs = SelectTables(itemsize, tensor_extent(scratch), tensor_extent(dev_out))
+            boxes = []
+            for j, k in enumerate(idx):
+                boxes.append((getters[k], spec, csel, _slot_sel(whole, j, s0), False))
+                tabs.add_points(int(ix.counts[k]), int(ix.first[k]), j * slot_bytes, slot_bytes, (n - 1) * ostride)
+            if direct:
+                p = pipe.prepare_read(boxes, scratch)
+                p.launch()
+                progs.append(p)
+                groups.append(idx)
+            else:
+                for i, r in zip(idx, pipe.read_sync(boxes, scratch)):
+                    results[i] = r
+            keep.append(tabs.launch(scratch, dev_out, device, table=table))
+        if progs:  # ONE readback of every launch's error and verdict words, after the last gather
+            for i, r in enumerate(ProgramGroup(progs, groups, len(getters)).results_fast()):
+                if r is not None:
+                    results[i] = r
+    del keep, table
+    return tuple(results)
+
+
+def write_points(pipe, getters, spec, ix, value, distinct: bool, partial_encode: bool = True) -> None:
+    """A coordinate or mask write planned on the device: every touched chunk
+    is decoded whole into its slot (a missing chunk gives fill, a CRC mismatch
+    raises before anything of its sub-batch is stored), k_select_copy scatters
+    value into the slots, and the chunks are written back whole through the
+    basic write path.  distinct: the points are known to differ (a mask's
+    nonzero coordinates).  Repeated destinations are not dropped on the
+    device, so a coordinate write takes a scalar value only: equal values
+    racing to one address."""
+    from .buffer import torch_dtype
+    from .pipeline import _resolve_value, _torch
+    from .writer import _value_tensor
+
+    torch = _torch()
+    whole, csel = _points_setup(pipe, spec, ix, len(getters))
+    value = _resolve_value(value)
+    scalar = (isinstance(value, torch.Tensor) and value.dim() == 0) or \
+        (not isinstance(value, torch.Tensor) and np.ndim(value) == 0)
+    if not scalar and not distinct:
+        raise NotImplementedError("a coordinate write through device indices with an array value: repeated "
+                                  "coordinates need a keep-last pass on the device, which is not built; pass "
+                                  "the indices as host (numpy) arrays, or write a scalar")
+    device = ix.device
+    itemsize = np.dtype(spec.dtype).itemsize
+    n = ix.n
+    if n == 0:
+        return
+    with torch.cuda.device(device):
+        v = _value_tensor(value, spec.dtype, device)
+        v = v.reshape(1) if scalar else v
+        if not scalar and (v.dim() != 1 or v.numel() != n):
+            raise ValueError(f"value of shape {tuple(v.shape)} for a selection of {n} points")
+        vstride = 0 if scalar else int(v.stride(0)) * itemsize
+        s0 = spec.shape[0]
+        cstr = _scratch_strides(spec, itemsize)
+        slot_bytes = cstr[0] * s0
+        per = _slots(spec, len(getters))
+        direct = _direct(pipe)
+        scratch = torch.empty((per * s0,) + tuple(spec.shape[1:]), dtype=torch_dtype(spec.dtype), device=device)
+        table = ix.build_table(cstr, vstride, True)
+        for at in range(0, len(getters), per):
+            rbatch, wbatch = [], []
+            tabs = SelectTables(itemsize, tensor_extent(v), tensor_extent(scratch))
+            for j, k in enumerate(range(at, min(at + per, len(getters)))):
+                osel = _slot_sel(whole, j, s0)
+                rbatch.append((getters[k], spec, csel, osel, False))
+                wbatch.append((getters[k], spec, csel, osel, True))
+                tabs.add_points(int(ix.counts[k]), int(ix.first[k]), j * slot_bytes, slot_bytes, (n - 1) * vstride,
+                                write=True)
+            if direct:
+                p = pipe.prepare_read(rbatch, scratch)
+                p.launch()
+                up = tabs.launch(v, scratch, device, table=table)
+                p.results_fast()  # a checksum mismatch raises here: nothing stored yet
+                del up
+            else:
+                pipe.read_sync(rbatch, scratch)
+                tabs.launch(v, scratch, device, table=table)
+            pipe._write_sync(wbatch, scratch, (), partial_encode)
+        del table
