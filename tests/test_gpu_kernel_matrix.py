@@ -10,14 +10,16 @@ of a selection rule fails a row here and has to be acknowledged in the table.
 Shipped library only: nothing here forces a tuning arm.
 
 Units are 32 KiB, steps 4 KiB; nseg = units per chunk.  The rules as of this
-table (csrc/decode.hip launch_decode, csrc/capi.cpp il_tiles / il_widest):
+table (csrc/decode.hip launch_decode -> launch_row_units, csrc/capi.cpp
+il_tiles / il_widest):
   nseg % 8 == 0 (interleaved layouts; S = 32 / 16 / 8, the widest that tiles)
       launch <= 512 units, nseg <= 32, fewer chunks than CUs   k_decode_ilh
       launch <= 512 units otherwise (nseg <= 256)              k_decode_ilw512
       launch  > 512 units                                      k_decode_il
   otherwise, nseg > 32                                         k_decode_duo
   otherwise                                                    k_decode_pair
-and (csrc/encode.hip launch_encode) nseg % 8 == 0 and nseg <= 32 k_encode_il,
+and (csrc/encode.hip launch_encode -> launch_encode_rows) nseg % 8 == 0 and
+nseg <= 32 k_encode_il,
 every other row layout of more than 16 KiB k_encode_pair."""
 
 from collections import namedtuple

@@ -1097,9 +1097,9 @@ int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size
     // arms 69 / 70 / 71 force 16 / 32 / 8
     int si = plan->off_il_s[1] ? 1 : plan->off_il_s[0] ? 0 : -1;
 #if ZHIP_TUNING
-    if (g_tune_arm == 69) si = plan->off_il_s[0] ? 0 : -1;
-    if (g_tune_arm == 70) si = plan->off_il_s[1] ? 1 : -1;
-    if (g_tune_arm == 71) si = -1;
+    if (g_tune_arm == kArmIlS16) si = plan->off_il_s[0] ? 0 : -1;
+    if (g_tune_arm == kArmIlS32) si = plan->off_il_s[1] ? 1 : -1;
+    if (g_tune_arm == kArmIlS8) si = -1;
 #endif
     if (p.il_S && si >= 0) {  // groups of 16 / 32 workgroups: the plan's second / third table set
         p.il_S = 16u << si;
@@ -1125,9 +1125,10 @@ int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size
     {
         int wi = (n_index == 0 || plan->idx_E <= (uint32_t)kWgStride) && units <= kIlwMaxUnits ? 1 : -1;
 #if ZHIP_TUNING
-        if (g_tune_arm == 26 || g_tune_arm == 31) wi = 0;
-        else if (g_tune_arm == 27 || g_tune_arm == 32 || g_tune_arm == 42) wi = 1;
-        if (((g_tune_arm >= 26 && g_tune_arm <= 32) || g_tune_arm == 42) &&
+        if (g_tune_arm == kArmIlw1024 || g_tune_arm == kArmIlw1024Reg) wi = 0;
+        else if (g_tune_arm == kArmIlw512 || g_tune_arm == kArmIlw512Reg || g_tune_arm == kArmIlw512Half) wi = 1;
+        // (the probes' numbers lie inside the ilw arms' range)
+        if ((arm_in(kArmIlw1024, kArmIlw512Reg) || g_tune_arm == kArmIlw512Half) &&
             !(n_index == 0 || plan->idx_E <= (uint32_t)kWgStride)) wi = -1;
 #endif
         p.ilw_nt = (wi >= 0 && plan->off_ilw[wi]) ? (1024u >> wi) : 0u;
@@ -1142,7 +1143,7 @@ int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size
     // whole-chunk row map is affine: the row kernels compute destinations
     // (tuning arm 45 keeps the map loads: the A/B reference)
     p.aff_ok = (decode_flags & ZHIP_DF_WHOLE) && (decode_flags & ZHIP_DF_ROWS) && d_rowmap && plan->aff_ok &&
-               !(ZHIP_TUNING && g_tune_arm == 45);
+               !(ZHIP_TUNING && g_tune_arm == kArmRowMap);
     if (p.aff_ok) set_affine(p, plan);
     for (int op = 0; op < 4; ++op) p.hx[op] = plan->hx[op];
     for (int i = 0; i < 32; ++i) p.kq[i] = plan->kq[i];
@@ -1226,7 +1227,8 @@ int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size
             if (plan->tile4f && (g_tune_bits & kTuneTile4F)) {  // arm: measured 0.3-0.4 us slower on C3
                 p.t4f_tab = plan->d_tile_tables + plan->tile4f_off;
                 p.t4f_kq = p.t4f_tab + kPairTabWords;
-            } else if (plan->tile4w && g_tune_arm != 1 && g_tune_arm != 2 && g_tune_arm != 5) {
+            } else if (plan->tile4w && g_tune_arm != kArmPub16 && g_tune_arm != kArmDeferred &&
+                       g_tune_arm != kArmNoWaveTile) {
                 // production for CRC layouts: a wave per tile, one chain per lane (k_decode_tile4w:
                 // C3 28.9 vs 30.3-30.6 us, profiles/r04/k); arms 1 / 2 / 5: k_decode_tile4
                 p.t4w_tab = plan->d_tile_tables + plan->tile4w_off;
@@ -1235,7 +1237,7 @@ int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size
                 if (plan->tile2w_off) p.t2w_kq = plan->d_tile_tables + plan->tile2w_off;
                 if (plan->tile1w_off) p.t1w_kq = plan->d_tile_tables + plan->tile1w_off;
             }
-        } else if (plan->tile2 && plan->tile2_off && !(g_tune_bits & kTuneTile1) && g_tune_arm == 39) {
+        } else if (plan->tile2 && plan->tile2_off && !(g_tune_bits & kTuneTile1) && g_tune_arm == kArmTilePairs) {
             // consecutive tile pairs (k_decode_tile4w<2>) where tile4 declines
             // (tuning arm 39; the grouped kernels are faster)
             p.tile2 = 1;
@@ -1252,7 +1254,8 @@ int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size
             p.n_sub = plan->n_sub;
             p.g_step_t = plan->sstride[plan->gd];
             p.g_step_o = L.out_stride[plan->gd];
-            if (plan->tilegw && g_tune_arm != 2 && g_tune_arm != 5) {  // a wave per tile, one chain per lane
+            // a wave per tile, one chain per lane
+            if (plan->tilegw && g_tune_arm != kArmDeferred && g_tune_arm != kArmNoWaveTile) {
                 p.t4w_tab = plan->d_tile_tables + plan->tilegw_off;
                 p.t4w_kq = p.t4w_tab + kPairTabWords;
                 if (plan->tileg2w_off) p.t2w_kq = plan->d_tile_tables + plan->tileg2w_off;  // two tiles per workgroup
@@ -1295,7 +1298,7 @@ int zhip_encode_mapped(const zhip_plan* plan, const void* arr, void* dst, const 
     EncodeParams p{};
     // chunks' publication words a 128-byte line apart (zhip_plan_info's >= kPubLine
     // workspace words for CRC layouts); arm ZHIP_TUNE_ARM = 9: 16 bytes apart
-    p.pub_stride = ((plan->layout.flags & ZHIP_LF_CRC) && g_tune_arm != 9) ? kPubLine / 2u : 2u;
+    p.pub_stride = ((plan->layout.flags & ZHIP_LF_CRC) && g_tune_arm != kArmEncPub16) ? kPubLine / 2u : 2u;
     p.arr = static_cast<const uint8_t*>(arr);
     p.dst = static_cast<uint8_t*>(dst);
     p.chunks = d_chunks;
@@ -1395,14 +1398,14 @@ int zhip_encode_mapped(const zhip_plan* plan, const void* arr, void* dst, const 
             // the decode's widest interleave (S = 32 / 16 where the steps tile
             // it; tuning arm 73 keeps S = 8)
             int si = plan->off_il_s[1] ? 1 : plan->off_il_s[0] ? 0 : -1;
-            if (ZHIP_TUNING && g_tune_arm == 73) si = -1;
+            if (ZHIP_TUNING && g_tune_arm == kArmEncIlS8) si = -1;
             p.il_S = si >= 0 ? 16u << si : plan->il_S;
             p.il_tab = plan->d_tables + (si >= 0 ? plan->off_il_s[si] : plan->off_il);
             p.il_klane = p.il_tab + kPairTabWords;
             // whole-chunk selections: destinations computed (ZHIP_DF_WHOLE, as the
             // decode) only in tuning arm 46 -- graph-timed 29.1 vs 28.6 us on the
             // C2 encode (profiles/r05/x/): the encode keeps the row map
-            p.aff_ok = (encode_flags & ZHIP_DF_WHOLE) && plan->aff_ok && ZHIP_TUNING && g_tune_arm == 46;
+            p.aff_ok = (encode_flags & ZHIP_DF_WHOLE) && plan->aff_ok && ZHIP_TUNING && g_tune_arm == kArmEncAff;
             if (p.aff_ok) set_affine(p, plan);
         }
     }

@@ -34,6 +34,7 @@
 #include "../../include/zarrhip.h"
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
+#include "zhip_dispatch.h"
 #include "zhip_device.h"
 #include "zhip_decode_common.h"
 
@@ -449,17 +450,11 @@ __global__ __launch_bounds__(kThreads) void k_decode_tile(const DecodeParams p) 
     }
 }
 
-using KernelFn = void (*)(const DecodeParams);
-
 template <bool CRC, bool WRITE, bool FAST, int K>
 static KernelFn pick_item(int item, bool swap) {
-    switch (item) {
-        case 1: return k_decode<CRC, WRITE, FAST, 1, false, K>;
-        case 2: return swap ? k_decode<CRC, WRITE, FAST, 2, true, K> : k_decode<CRC, WRITE, FAST, 2, false, K>;
-        case 4: return swap ? k_decode<CRC, WRITE, FAST, 4, true, K> : k_decode<CRC, WRITE, FAST, 4, false, K>;
-        case 8: return swap ? k_decode<CRC, WRITE, FAST, 8, true, K> : k_decode<CRC, WRITE, FAST, 8, false, K>;
-        default: return nullptr;
-    }
+    return for_item(item, swap, [](auto t) -> KernelFn {
+        return k_decode<CRC, WRITE, FAST, decltype(t)::item, decltype(t)::swap, K>;
+    });
 }
 
 KernelFn select_decode_kernel(bool crc, bool write, bool fast, int item, bool swap, int k) {
@@ -478,41 +473,11 @@ KernelFn select_decode_kernel(bool crc, bool write, bool fast, int item, bool sw
 }
 
 static KernelFn select_tile_kernel(bool crc, int item, bool swap) {
-    switch (item) {
-        case 1: return crc ? k_decode_tile<true, 1, false> : k_decode_tile<false, 1, false>;
-        case 2: return crc ? (swap ? k_decode_tile<true, 2, true> : k_decode_tile<true, 2, false>)
-                           : (swap ? k_decode_tile<false, 2, true> : k_decode_tile<false, 2, false>);
-        case 4: return crc ? (swap ? k_decode_tile<true, 4, true> : k_decode_tile<true, 4, false>)
-                           : (swap ? k_decode_tile<false, 4, true> : k_decode_tile<false, 4, false>);
-        case 8: return crc ? (swap ? k_decode_tile<true, 8, true> : k_decode_tile<true, 8, false>)
-                           : (swap ? k_decode_tile<false, 8, true> : k_decode_tile<false, 8, false>);
-        default: return nullptr;
-    }
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        return crc ? k_decode_tile<true, T::item, T::swap> : k_decode_tile<false, T::item, T::swap>;
+    });
 }
-
-KernelFn select_rows_kernel(bool crc, int item, bool swap, int k);  // decode_rows.hip
-KernelFn select_pair_kernel(bool crc, int item, bool swap, int nu);  // decode_rows.hip
-KernelFn select_duo_kernel(bool crc, int item, bool swap);           // decode_rows.hip
-KernelFn select_il_kernel(bool crc, int item, bool swap, bool aff);  // decode_rows.hip
-KernelFn select_ilw_kernel(int item, bool swap, int nt, bool lmr, bool aff);  // decode_rows.hip
-KernelFn select_ilh_kernel(int item, bool swap, bool lb, bool aff);  // decode_rows.hip
-#if ZHIP_TUNING
-KernelFn select_il_kernel_lean(bool crc, int item, bool swap);       // decode_rows.hip
-KernelFn select_il_kernel_tuned(bool crc, int item, bool swap);      // decode_rows.hip
-KernelFn select_il_kernel_arm(bool crc, int item, bool swap, int arm);  // decode_rows.hip
-KernelFn select_il_kernel_cf(bool crc, int item, bool swap);         // decode_rows.hip
-KernelFn select_il_kernel_regmul(bool crc, int item, bool swap, bool occ6);  // decode_rows.hip
-KernelFn select_xw_kernel(bool crc, int item, bool swap);            // decode_rows.hip
-KernelFn select_ilq_kernel(int item, bool swap, int nq, bool glds);  // decode_rows.hip
-KernelFn select_ilc_kernel(int item, bool swap);                     // decode_rows.hip
-KernelFn select_ilp_kernel(int item, bool swap);                     // decode_rows.hip
-KernelFn select_tile4f_kernel(int item, bool swap);                  // decode_tile.hip
-#endif
-KernelFn select_tile4_kernel(bool crc, int item, bool swap);         // decode_tile.hip
-KernelFn select_tile4w_kernel(int item, bool swap);                  // decode_tile.hip
-KernelFn select_tile2w_kernel(int item, bool swap, int nt);          // decode_tile.hip
-KernelFn select_tilegw_kernel(int item, bool swap, bool defer, int nt);  // decode_tile.hip
-KernelFn select_tileg_kernel(bool crc, int item, bool swap, bool defer);  // decode_tile.hip
 
 // name of the kernel the last launch_decode chose (zhip_last_kernel: bench
 // labels and tests; the selection depends on layout, plan and tuning bits)
@@ -545,391 +510,347 @@ __global__ __launch_bounds__(kThreads) void k_probe(const DecodeParams p) {
 #endif
 
 
-int launch_decode(const DecodeParams& p, hipStream_t stream, int max_grid) {
+// One launch_decode call: the parameters, where and how wide to launch, and
+// what every layout function reads of them.
+struct Launch {
+    const DecodeParams& p;
+    hipStream_t stream;
+    int max_grid;    // CUs * 8 (or ZHIP_TUNE_MAX_GRID)
+    uint32_t tune;   // the ablation bits: a compile-time 0 outside the tuning build
     // the look-back finalizer (publish_lb) waits only while fewer chunks than
-    // CUs are in the launch (max_grid arrives as CUs * 8)
-    const bool lb_ok = p.n_chunks < (uint32_t)(max_grid / 8);
-    (void)lb_ok;
+    // CUs are in the launch
+    bool lb_ok;
+    bool crc, swap;
+    int item;
+};
+
+// one workgroup per unit, or the fused index checks if there are more of them
+static uint32_t unit_grid(const DecodeParams& p, uint32_t units) { return units > p.n_idx ? units : p.n_idx; }
+
+// chunks of <= 16 KiB (sharded or not, with a CRC or not): four per
+// workgroup over their live steps, after the leading index-check
+// workgroups if any (k_decode_lead4; arm 11 keeps the pair kernels)
+// (chunks of 4-8 KiB: eight per workgroup over their last two steps;
+// graph-timed on the example array unsharded, profiles/r04/lead8/:
+// 8 KiB chunks 25.3-25.6 us vs 37.1 with four per workgroup and 30.8
+// with the pair kernel; 4 KiB chunks 37.2 with four, 52.4 with eight,
+// 41.4 with the pair kernel.  Arms 12 / 13 force four / eight.)
+// (k_decode_lead8 covers at most two steps: arm 13 cannot force it
+// onto chunks of more than 8 KiB)
+static int launch_lead4(const Launch& L) {
+    const DecodeParams& p = L.p;
+    const bool e8 = p.E <= 2u * kWgStride &&
+                    (g_tune_arm == kArmLead8 || (g_tune_arm != kArmLead4 && p.E > (uint32_t)kWgStride));
+    KernelFn fn = select_pair_kernel(L.crc, L.item, L.swap, e8 ? kPairLead8 : kPairLead4);
+    const uint32_t per = e8 ? 8u : 4u;
+    const uint32_t quads = (uint32_t)(((uint64_t)p.n_units + per - 1u) / per);
+    const uint32_t lead = (p.n_idx + 7u) & ~7u;
+    if ((uint64_t)quads + lead > 0x7FFFFFFFull) return ZHIP_E_UNSUPPORTED;
+    return fire(fn, e8 ? "k_decode_lead8" : "k_decode_lead4", quads + lead, kThreads, p, L.stream);
+}
+
+// k_decode_pair's XCD-contiguous runs: one resident wave of workgroups (4 per
+// CU; max_grid = 8 per CU), the workgroups of one XCD on a contiguous eighth
+// of the batch
+static DecodeParams with_xcd_runs(const Launch& L, uint32_t pairs, bool on) {
+    DecodeParams q = L.p;
+    q.xcd_run = (on && !(L.tune & kTuneNoXcd) && pairs % 8u == 0u && pairs <= (uint32_t)(L.max_grid / 8) * 4u)
+                    ? pairs / 8u : 0u;
+    q.h.xcd_run = q.xcd_run;
+    q.h.d_xcd = make_fdiv(q.xcd_run ? q.xcd_run : 1u);
+    return q;
+}
+
+// inner chunks without a CRC, shard indexes with one (zarr's default
+// sharding codecs): leading index-check workgroups, then the pairs
+// (k_decode_lead); > 32 units per chunk is not fused
+static int launch_lead(const Launch& L) {
+    const DecodeParams& p = L.p;
+    if (p.nseg > 32u) return ZHIP_E_UNSUPPORTED;
+    KernelFn fn = select_pair_kernel(false, L.item, L.swap, kPairLead);
+    const uint32_t pairs = (uint32_t)(((uint64_t)p.n_units + 1u) / 2u);
+    const uint32_t lead = (p.n_idx + 7u) & ~7u;
+    if ((uint64_t)pairs + lead > 0x7FFFFFFFull) return ZHIP_E_UNSUPPORTED;
+    return fire(fn, "k_decode_lead", pairs + lead, kThreads, with_xcd_runs(L, pairs, true), L.stream);
+}
+
+#if ZHIP_TUNING
+// The measurement arms of the whole-row layouts that launch a kernel of their
+// own (il: production would take an interleaved kernel).  True: the arm took
+// the launch, rc is its result.
+static bool launch_row_arm(const Launch& L, bool il, int& rc) {
+    const DecodeParams& p = L.p;
+    const uint32_t tune = L.tune;
+    const uint32_t units = unit_grid(p, p.n_units);
+    if (p.xw != 0 && L.crc && (tune & kTuneXw) &&
+        !(tune & (kTuneNoXw | kTuneSkipCrc | kTuneSingle | kTuneDuo | kTuneIl))) {
+        const uint64_t xg = (uint64_t)((p.n_chunks + 3u) / 4u) * p.xw;
+        const uint64_t grid = xg > p.n_idx ? xg : p.n_idx;
+        rc = grid > 0x7FFFFFFFull ? ZHIP_E_UNSUPPORTED
+                                  : fire(select_xw_kernel(L.crc, L.item, L.swap), "k_decode_xw", (uint32_t)grid,
+                                         kThreads, p, L.stream);
+        return true;
+    }
+    if (arm_in(kArmProbeArgs, kArmProbeHeader)) {  // overhead probes
+        KernelFn pf = g_tune_arm == kArmProbeArgs ? k_probe<0> : g_tune_arm == kArmProbeLds ? k_probe<1> : k_probe<2>;
+        rc = fire(pf, g_tune_arm == kArmProbeArgs ? "k_probe_args"
+                      : g_tune_arm == kArmProbeLds ? "k_probe_lds" : "k_probe_header",
+                  units, kThreads, p, L.stream);
+        return true;
+    }
+    if (L.crc && p.ilw_nt && (g_tune_arm == kArmIlw1024 || g_tune_arm == kArmIlw512 || g_tune_arm == kArmIlw1024Reg ||
+                              g_tune_arm == kArmIlw512Reg || g_tune_arm == kArmIlw512Half)) {
+        // k_decode_ilw: one 32 KiB unit per workgroup of 1024 / 512 lanes
+        // (31 / 32: the lane multiply in registers; 42: half in registers)
+        const bool half = g_tune_arm == kArmIlw512Half;
+        const bool reg = g_tune_arm == kArmIlw1024Reg || g_tune_arm == kArmIlw512Reg;
+        KernelFn fn = half ? select_ilw_kernel(L.item, L.swap, kIlw512Half, false, false)
+                           : select_ilw_kernel(L.item, L.swap, p.ilw_nt == 1024u ? kIlw1024 : kIlw512, reg, p.aff_ok != 0);
+        rc = fire(fn, half ? "k_decode_ilw512m"
+                      : p.ilw_nt == 1024u ? (reg ? "k_decode_ilw1024r" : "k_decode_ilw1024")
+                                          : (reg ? "k_decode_ilw512r" : "k_decode_ilw512"),
+                  units, p.ilw_nt, p, L.stream);
+        return true;
+    }
+    if (!il) return false;
+    if ((g_tune_arm == kArmIlh || g_tune_arm == kArmIlhLookBack) && p.ilh_klane) {  // k_decode_ilh: 16 KiB per workgroup
+        // (59: with the look-back finalizer, at most 64 half units per chunk)
+        KernelFn fn = select_ilh_kernel(L.item, L.swap, g_tune_arm == kArmIlhLookBack && L.lb_ok && p.nseg <= 32u, false);
+        rc = fire(fn, "k_decode_ilh", unit_grid(p, 2u * p.n_units), kThreads, p, L.stream);
+        return true;
+    }
+    if (g_tune_arm == kArmIlp && p.pred) {  // k_decode_ilp: index entry off the stores' path
+        rc = fire(select_ilp_kernel(L.item, L.swap), "k_decode_ilp", units, kThreads, p, L.stream);
+        return true;
+    }
+    if (g_tune_arm == kArmIlc) {  // k_decode_ilc: tables built in LDS, predicted loads first
+        rc = fire(select_ilc_kernel(L.item, L.swap), "k_decode_ilc", units, kThreads, p, L.stream);
+        return true;
+    }
+    if (arm_in(kArmIlq2, kArmIlq4Glds)) {
+        // k_decode_ilq arms: NQ units per workgroup, tables by registers or LDS-DMA
+        static const char* names[] = {"k_decode_ilq2", "k_decode_ilq4", "k_decode_ilq1_glds",
+                                      "k_decode_ilq2_glds", "k_decode_ilq4_glds"};
+        const int a = g_tune_arm - kArmIlq2;
+        const int nq = (a == 0 || a == 3) ? 2 : (a == 1 || a == 4) ? 4 : 1;
+        const uint32_t ug = (uint32_t)(((uint64_t)p.n_units + nq - 1u) / nq);
+        const uint32_t xg = (p.n_idx + (uint32_t)nq - 1u) / (uint32_t)nq;
+        rc = p.nseg % (uint32_t)nq ? ZHIP_E_UNSUPPORTED
+                                   : fire(select_ilq_kernel(L.item, L.swap, nq, a >= 2), names[a], ug > xg ? ug : xg,
+                                          nq * kThreads, p, L.stream);
+        return true;
+    }
+    return false;
+}
+#endif
+
+// k_decode_il's instantiation: production, or in the tuning build the arm's
+// (nullptr where the arm has none for this item type)
+static KernelFn pick_il_kernel(const Launch& L) {
+#if ZHIP_TUNING
+    const DecodeParams& p = L.p;
+    const uint32_t tune = L.tune;
+    // (arms 1 / 2 are k_decode_il's own; every other arm keeps production here)
+    // (58: the look-back finalizer, while fewer chunks than CUs)
+    if (g_tune_arm == kArmPub16 || g_tune_arm == kArmDeferred ||
+        ((g_tune_arm == kArmSplitPub || arm_in(kArmIlPrioRunEnd, kArmIlXcd) ||
+          (g_tune_arm == kArmLookBack && L.lb_ok && p.nseg <= 32u) ||
+          g_tune_arm == kArmIlStoreWt || g_tune_arm == kArmIlStoreNt) && p.aff_ok))
+        return select_il_kernel_arm(L.crc, L.item, L.swap, g_tune_arm);
+    if (tune & kTuneCfLookup) return select_il_kernel_cf(L.crc, L.item, L.swap);
+    if (tune & kTuneIlLean) return select_il_kernel_lean(L.crc, L.item, L.swap);
+    if (tune & (kTuneIlRegMul | kTuneIlOcc6))
+        return select_il_kernel_regmul(L.crc, L.item, L.swap, (tune & kTuneIlOcc6) != 0);
+    if (tune & (kTuneNoTables | kTuneNoRunEnd | kTuneNoPub | kTuneStamp))
+        return select_il_kernel_tuned(L.crc, L.item, L.swap);
+#endif
+    return select_il_kernel(L.crc, L.item, L.swap, L.p.aff_ok != 0);
+}
+
+// k_decode_pair's instantiation for nu units per workgroup: production, or
+// in the tuning build the variant the ablation bits ask for where it exists
+static KernelFn pick_pair_kernel(const Launch& L, int nu) {
+#if ZHIP_TUNING
+    const uint32_t tune = L.tune;
+    // (kTuneTrailingCrc / kTuneSplitChain are read by the production kernel itself)
+    if (nu == 2 && !(tune & (kTuneTrailingCrc | kTuneSplitChain))) {
+        KernelFn fn = (tune & kTuneSkipCrc) ? select_pair_kernel(L.crc, L.item, L.swap, kPairNoLookups)
+                      : (tune & (kTunePrio | kTuneDeferB))
+                          ? select_pair_kernel(L.crc, L.item, L.swap,
+                                               (tune & kTunePrio) && (tune & kTuneDeferB) ? kPairPrioDeferB
+                                               : (tune & kTunePrio) ? kPairPrio : kPairDeferB)
+                          : nullptr;
+        if (fn) return fn;
+    }
+#endif
+    return select_pair_kernel(L.crc, L.item, L.swap, nu == 2 ? kPairTwo : kPairSingle);
+}
+
+// Whole-row layouts with a row map, 32 KiB units: one workgroup per unit,
+// half unit or pair of units, non-persistent.  The production rule reads top
+// to bottom: lead4 / lead8, lead, ilh, ilw512, il, duo, pair.
+static int launch_row_units(const Launch& L) {
+    const DecodeParams& p = L.p;
+    const uint32_t tune = L.tune;
+    const bool crc = L.crc;
+    if (p.nseg == 1u && p.E <= 4u * kWgStride && g_tune_arm != kArmNoLead4) return launch_lead4(L);
+    if (!crc && p.n_idx) return launch_lead(L);
+    // chunks of a multiple of 8 x 32 KiB: interleaved steps in groups of
+    // eight workgroups (k_decode_il, see decode_rows.hip) -- graph-timed
+    // 26.4 vs 27.8 us on the headline; groups of four lose to the pair
+    // kernel at C4 (profiles/r03/il/).  kTuneIl / kTuneNoIl force.
+    const bool il = p.il_S != 0 && crc && !(tune & (kTuneNoIl | kTuneSkipCrc | kTuneSingle | kTuneDuo)) &&
+                    ((tune & kTuneIl) || p.il_S >= 8u);
+#if ZHIP_TUNING
+    int rc;
+    if (launch_row_arm(L, il, rc)) return rc;
+#endif
+    // grids of at most kIlwMaxUnits units (2 per CU: the N = 4 / 8 shares of
+    // the strong-scaled headline) with fewer chunks than CUs: half units of
+    // 16 KiB (k_decode_ilh, two workgroups per unit) publishing through the
+    // look-back finalizer -- graph-timed 8.39 vs 9.77 us (k_decode_ilw512)
+    // at the N = 8 share, 10.73 vs 11.03 at N = 4 (profiles/r06/a/).
+    // (Tuning build: arm 0 only; arm 58 / 49 keep k_decode_ilw512.)
+    if (il && p.ilh_klane && p.n_units <= kIlwMaxUnits && L.lb_ok && p.nseg <= 32u &&
+        (g_tune_arm == kArmProduction || g_tune_arm == kArmIlhProduction) && (tune & ~kTuneStamp) == 0)
+        return fire(select_ilh_kernel(L.item, L.swap, true, p.aff_ok != 0), "k_decode_ilh",
+                    unit_grid(p, 2u * p.n_units), kThreads, p, L.stream);
+    // otherwise 512 lanes per unit, four blocks per lane (k_decode_ilw,
+    // decode_rows.hip) -- graph-timed 8.8 vs 9.4 us at the N = 8 share, 10.3
+    // vs 11.0 at N = 4; 14.6 vs 16.5 for k_decode_il at N = 2
+    // (profiles/r05/f/).  (Tuning build: any arm keeps k_decode_il.)
+    if (il && p.ilw_nt == 512u && p.n_units <= kIlwMaxUnits &&
+        (g_tune_arm == kArmProduction || g_tune_arm == kArmRowMap || g_tune_arm == kArmIlw512Small ||
+         ((g_tune_arm == kArmSplitPub || g_tune_arm == kArmLookBack) && p.aff_ok)) &&
+        (tune & ~kTuneStamp) == 0) {
+        // (tuning arms, whole-chunk reads: 49 the split publication, 58 the
+        // look-back finalizer)
+        const IlwForm form = g_tune_arm == kArmSplitPub ? kIlw512Split
+                             : (g_tune_arm == kArmLookBack && L.lb_ok && p.nseg <= 64u) ? kIlw512LookBack : kIlw512;
+        return fire(select_ilw_kernel(L.item, L.swap, form, false, p.aff_ok != 0), "k_decode_ilw512",
+                    unit_grid(p, p.n_units), 512, p, L.stream);
+    }
+    if (il) return fire(pick_il_kernel(L), "k_decode_il", unit_grid(p, p.n_units), kThreads, p, L.stream);
+    // one workgroup per pair of units (k_decode_pair)
+    const int nu = (tune & kTuneSingle) ? 1 : 2;
+    KernelFn fn = pick_pair_kernel(L, nu);
+    if (!fn) return ZHIP_E_UNSUPPORTED;
+    // chunks of more than 32 units (> 1 MiB): one unit per 256-thread half of
+    // a 512-thread workgroup (k_decode_duo; C1 0.55 -> 0.62 of HBM peak,
+    // profiles/r02/kernel_arms_ab.jsonl); kTuneDuo forces it
+    if ((tune & kTuneDuo) || (p.nseg > 32 && !(tune & (kTuneSingle | kTuneSkipCrc))))
+        return fire(select_duo_kernel(crc, L.item, L.swap), "k_decode_duo",
+                    unit_grid(p, (uint32_t)(((uint64_t)p.n_units + 1u) / 2u)), 2 * kThreads, p, L.stream);
+    const uint32_t grid = unit_grid(p, (uint32_t)(((uint64_t)p.n_units + nu - 1u) / nu));
+    return fire(fn, "k_decode_pair", grid, kThreads, with_xcd_runs(L, grid, nu == 2), L.stream);
+}
+
+// The persistent kernels (k_decode_rows, k_decode_tile, k_decode): a resident
+// grid of workgroups, each over a balanced range of the units (software-
+// pipelined per workgroup); a launch without units does nothing
+static int launch_persistent(const Launch& L, KernelFn fn, const char* name) {
+    uint32_t grid = L.p.n_units;
+    if (fn && grid) {
+        const uint32_t resident = (uint32_t)resident_grid(fn, L.max_grid);
+        if (grid > resident) grid = resident;
+    }
+    return fire(fn, name, grid, kThreads, L.p, L.stream);
+}
+
+// four tiles per workgroup, non-persistent (k_decode_tile4, decode_tile.hip)
+// (arm kTuneTile4F: one A_64 chain per thread when the layout's tile step is
+// 256 B, k_decode_tile4f -- exact, measured 0.3-0.4 us slower on C3)
+static int launch_tile4(const Launch& L) {
+    const DecodeParams& p = L.p;
+    const bool f4 = ZHIP_TUNING && p.t4f_tab != nullptr && L.crc;
+    const bool w4 = !f4 && p.t4w_tab != nullptr && L.crc;
+    // two tiles per workgroup (2 048 workgroups on C3: two residency rounds
+    // instead of one) -- graph-timed 27.8-27.9 vs 28.4-30.0 us on C3
+    // (profiles/r05/l/); tuning arm 38 keeps four, 37 takes one (46 us)
+    if (w4 && ((p.t2w_kq && g_tune_arm != kArmTileFour && g_tune_arm != kArmTile1w) ||
+               (g_tune_arm == kArmTile1w && p.t1w_kq))) {
+        const bool one = g_tune_arm == kArmTile1w;
+        // (tuning arm 49: the split publication of 17..32 workgroups per chunk)
+        // (tuning arm 67: the byte-table chains, where the plan built them)
+        const Tile2wForm form = one ? kT2wOne : g_tune_arm == kArmSplitPub ? kT2wSplit
+                                : (g_tune_arm == kArmTile2wByteTab && p.tbt_tab) ? kT2wByteTab : kT2wTwo;
+        DecodeParams q = p;
+        q.t4w_kq = one ? p.t1w_kq : p.t2w_kq;
+        return fire(select_tile2w_kernel(L.item, L.swap, form),
+                    one ? "k_decode_tile1w" : form == kT2wSplit ? "k_decode_tile2ws"
+                    : form == kT2wByteTab ? "k_decode_tile2w_bt" : "k_decode_tile2w",
+                    p.n_units / (one ? 1u : 2u), kThreads, q, L.stream);
+    }
+#if ZHIP_TUNING
+    if (f4) return fire(select_tile4f_kernel(L.item, L.swap), "k_decode_tile4f", p.n_units / 4u, kThreads, p, L.stream);
+#endif
+    return fire(w4 ? select_tile4w_kernel(L.item, L.swap) : select_tile4_kernel(L.crc, L.item, L.swap),
+                w4 ? "k_decode_tile4w" : "k_decode_tile4", p.n_units / 4u, kThreads, p, L.stream);
+}
+
+// consecutive tile pairs (k_decode_tile4w<2>, decode_tile.hip): 128^3
+// chunks' two 256-byte column blocks of one row band per workgroup
+static int launch_tile_pairs(const Launch& L) {
+    const DecodeParams& p = L.p;
+    if (p.n_units / 2u >= (1u << 31)) return ZHIP_E_UNSUPPORTED;
+    return fire(select_tile2w_kernel(L.item, L.swap, kT2wTwo), "k_decode_tilep", p.n_units / 2u, kThreads, p, L.stream);
+}
+
+// tiles grouped by four along a stored dim (k_decode_tileg, decode_tile.hip)
+// (k_decode_tilegw when the plan's wave-per-tile chains are selected)
+static int launch_tile_groups(const Launch& L) {
+    const DecodeParams& p = L.p;
+    const bool gw = p.t4w_tab != nullptr && L.crc;
+    // (arm 2: the returning publication whatever the flags)
+    const bool defer = p.defer != 0 && g_tune_arm != kArmDeferred;
+    // two tiles per workgroup where the plan built their constants (as
+    // k_decode_tile4w); tuning arms 38 (deferred) / 2 (returning) keep four
+    TilegwForm form = (gw && p.t2w_kq && g_tune_arm != kArmTileFour && g_tune_arm != kArmDeferred &&
+                       g_tune_arm != kArmTilegLanes) ? kTgwTwo : kTgwFour;
+    const bool two = form == kTgwTwo;
+#if ZHIP_TUNING
+    if (gw && g_tune_arm == kArmTilegLanes && p.tglt_kq) form = kTgwLanes;  // four tiles, lanes pick the tile
+    if (two && g_tune_arm == kArmTilegPacked) form = kTgwPacked;  // the arrival words packed (round-4 layout)
+    // the look-back finalizer (fewer chunks than CUs; the spread subwords)
+    if (two && g_tune_arm == kArmTilegLookBack && L.lb_ok && p.n_groups <= 128u) form = kTgwLookBack;
+    if (two && g_tune_arm == kArmTilegByteTab && p.tbt_tab) form = kTgwByteTab;  // the byte-table chains
+#endif
+    KernelFn fn = gw ? select_tilegw_kernel(L.item, L.swap, defer, form)
+                     : select_tileg_kernel(L.crc, L.item, L.swap, defer);
+    const uint64_t grid = (uint64_t)p.n_chunks * p.n_groups * (two ? 2u : 1u);
+    if (grid >= (1ull << 31)) return ZHIP_E_UNSUPPORTED;
+    DecodeParams q = p;
+    if (two) q.t4w_kq = p.t2w_kq;
+    if (form == kTgwLanes) q.t4w_kq = p.tglt_kq;
+    return fire(fn, !gw ? "k_decode_tileg" : form == kTgwPacked ? "k_decode_tileg2wp"
+                    : form == kTgwLookBack ? "k_decode_tileg2w_lb" : form == kTgwByteTab ? "k_decode_tileg2w_bt"
+                    : two ? "k_decode_tileg2w" : form == kTgwLanes ? "k_decode_tileglt" : "k_decode_tilegw",
+                (uint32_t)grid, kThreads, q, L.stream);
+}
+
+// The kernel of a launch, by layout: whole-row units, persistent rows, the
+// tile kernels of transposed layouts (tile4, tile pairs, grouped tiles,
+// persistent tile), else the generic persistent k_decode.
+int launch_decode(const DecodeParams& p, hipStream_t stream, int max_grid) {
+    const bool crc = (p.lflags & ZHIP_LF_CRC) != 0;
+    const bool lb_ok = p.n_chunks < (uint32_t)(max_grid / 8);  // max_grid arrives as CUs * 8
     if (g_tune_max_grid > 0) max_grid = g_tune_max_grid;
-    // the ablation bits: a compile-time 0 outside the tuning build
-    const uint32_t tune = ZHIP_TUNING ? p.tune : 0u;
+    const Launch L = {p, stream, max_grid, ZHIP_TUNING ? p.tune : 0u, lb_ok, crc, (p.lflags & ZHIP_LF_SWAP) != 0,
+                      p.g.itemsize};
     // (the kTunePersist arm never applies to a launch carrying fused index
     // checks of CRC-free inner chunks: only k_decode_lead carries those)
-    const bool lead_launch = !(p.lflags & ZHIP_LF_CRC) && p.n_idx != 0;
+    const bool lead_launch = !crc && p.n_idx != 0;
     if (p.rows && p.rowmap && p.seg == (uint32_t)kWgStride * kDefaultBlocks &&
-        (!(tune & kTunePersist) || lead_launch)) {
-        // one workgroup per pair of units, non-persistent (k_decode_pair)
-        const int nu = (tune & kTuneSingle) ? 1 : 2;
-        const bool crc = (p.lflags & ZHIP_LF_CRC) != 0, swap = (p.lflags & ZHIP_LF_SWAP) != 0;
-        if (p.nseg == 1u && p.E <= 4u * kWgStride && g_tune_arm != 11) {
-            // chunks of <= 16 KiB (sharded or not, with a CRC or not): four per
-            // workgroup over their live steps, after the leading index-check
-            // workgroups if any (k_decode_lead4; arm 11 keeps the pair kernels)
-            // (chunks of 4-8 KiB: eight per workgroup over their last two steps;
-            // graph-timed on the example array unsharded, profiles/r04/lead8/:
-            // 8 KiB chunks 25.3-25.6 us vs 37.1 with four per workgroup and 30.8
-            // with the pair kernel; 4 KiB chunks 37.2 with four, 52.4 with eight,
-            // 41.4 with the pair kernel.  Arms 12 / 13 force four / eight.)
-            // (k_decode_lead8 covers at most two steps: arm 13 cannot force it
-            // onto chunks of more than 8 KiB)
-            const bool e8 = p.E <= 2u * kWgStride &&
-                            (g_tune_arm == 13 || (g_tune_arm != 12 && p.E > (uint32_t)kWgStride));
-            KernelFn qfn = select_pair_kernel(crc, p.g.itemsize, swap, e8 ? 11 : 10);
-            if (!qfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t per = e8 ? 8u : 4u;
-            const uint32_t quads = (uint32_t)(((uint64_t)p.n_units + per - 1u) / per);
-            const uint32_t lead = (p.n_idx + 7u) & ~7u;
-            if ((uint64_t)quads + lead > 0x7FFFFFFFull) return ZHIP_E_UNSUPPORTED;
-            g_last_kernel = e8 ? "k_decode_lead8" : "k_decode_lead4";
-            hipLaunchKernelGGL(qfn, dim3(quads + lead), dim3(kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        if (!crc && p.n_idx) {
-            // inner chunks without a CRC, shard indexes with one (zarr's default
-            // sharding codecs): leading index-check workgroups, then the pairs
-            // (k_decode_lead); > 32 units per chunk is not fused
-            if (p.nseg > 32u) return ZHIP_E_UNSUPPORTED;
-            KernelFn lfn = select_pair_kernel(false, p.g.itemsize, swap, 9);
-            if (!lfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t pairs = (uint32_t)(((uint64_t)p.n_units + 1u) / 2u);
-            const uint32_t lead = (p.n_idx + 7u) & ~7u;
-            if ((uint64_t)pairs + lead > 0x7FFFFFFFull) return ZHIP_E_UNSUPPORTED;
-            DecodeParams q = p;
-            q.xcd_run = (!(tune & kTuneNoXcd) && pairs % 8u == 0u && pairs <= (uint32_t)(max_grid / 8) * 4u)
-                            ? pairs / 8u : 0u;
-            q.h.xcd_run = q.xcd_run;
-            q.h.d_xcd = make_fdiv(q.xcd_run ? q.xcd_run : 1u);
-            g_last_kernel = "k_decode_lead";
-            hipLaunchKernelGGL(lfn, dim3(pairs + lead), dim3(kThreads), 0, stream, q);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        // chunks of a multiple of 8 x 32 KiB: interleaved steps in groups of
-        // eight workgroups (k_decode_il, see decode_rows.hip) -- graph-timed
-        // 26.4 vs 27.8 us on the headline; groups of four lose to the pair
-        // kernel at C4 (profiles/r03/il/).  kTuneIl / kTuneNoIl force.
-        const bool il = p.il_S != 0 && crc && !(tune & (kTuneNoIl | kTuneSkipCrc | kTuneSingle | kTuneDuo)) &&
-                        ((tune & kTuneIl) || p.il_S >= 8u);
-#if ZHIP_TUNING
-        const bool xw = p.xw != 0 && crc && (tune & kTuneXw) &&
-                        !(tune & (kTuneNoXw | kTuneSkipCrc | kTuneSingle | kTuneDuo | kTuneIl));
-        if (xw) {
-            KernelFn xfn = select_xw_kernel(crc, p.g.itemsize, swap);
-            if (!xfn) return ZHIP_E_UNSUPPORTED;
-            const uint64_t xg = (uint64_t)((p.n_chunks + 3u) / 4u) * p.xw;
-            const uint64_t grid = xg > p.n_idx ? xg : p.n_idx;
-            if (grid == 0) return ZHIP_OK;
-            if (grid > 0x7FFFFFFFull) return ZHIP_E_UNSUPPORTED;
-            g_last_kernel = "k_decode_xw";
-            hipLaunchKernelGGL(xfn, dim3((uint32_t)grid), dim3(kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        if (g_tune_arm >= 28 && g_tune_arm <= 30) {  // overhead probes
-            const uint32_t pgrid = p.n_units > p.n_idx ? p.n_units : p.n_idx;
-            if (pgrid == 0) return ZHIP_OK;
-            KernelFn pf = g_tune_arm == 28 ? k_probe<0> : g_tune_arm == 29 ? k_probe<1> : k_probe<2>;
-            g_last_kernel = g_tune_arm == 28 ? "k_probe_args" : g_tune_arm == 29 ? "k_probe_lds" : "k_probe_header";
-            hipLaunchKernelGGL(pf, dim3(pgrid), dim3(kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        if (crc && p.ilw_nt && (g_tune_arm == 26 || g_tune_arm == 27 || g_tune_arm == 31 || g_tune_arm == 32 ||
-                                g_tune_arm == 42)) {
-            // k_decode_ilw: one 32 KiB unit per workgroup of 1024 / 512 lanes
-            // (31 / 32: the lane multiply in registers; 42: half in registers)
-            KernelFn wfn = g_tune_arm == 42
-                               ? select_ilw_kernel(p.g.itemsize, swap, 513, false, false)
-                               : select_ilw_kernel(p.g.itemsize, swap, (int)p.ilw_nt, g_tune_arm >= 31, p.aff_ok != 0);
-            if (!wfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t wgrid = p.n_units > p.n_idx ? p.n_units : p.n_idx;
-            if (wgrid == 0) return ZHIP_OK;
-            g_last_kernel = g_tune_arm == 42 ? "k_decode_ilw512m"
-                            : p.ilw_nt == 1024u ? (g_tune_arm >= 31 ? "k_decode_ilw1024r" : "k_decode_ilw1024")
-                                                : (g_tune_arm >= 31 ? "k_decode_ilw512r" : "k_decode_ilw512");
-            hipLaunchKernelGGL(wfn, dim3(wgrid), dim3(p.ilw_nt), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        if (il && (g_tune_arm == 41 || g_tune_arm == 59) && p.ilh_klane) {  // k_decode_ilh: 16 KiB per workgroup
-            // (59: with the look-back finalizer, at most 64 half units per chunk)
-            KernelFn hfn = select_ilh_kernel(p.g.itemsize, swap, g_tune_arm == 59 && lb_ok && p.nseg <= 32u, false);
-            if (!hfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t hunits = 2u * p.n_units;
-            const uint32_t hgrid = hunits > p.n_idx ? hunits : p.n_idx;
-            if (hgrid == 0) return ZHIP_OK;
-            g_last_kernel = "k_decode_ilh";
-            hipLaunchKernelGGL(hfn, dim3(hgrid), dim3(kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        if (il && g_tune_arm == 35 && p.pred) {  // k_decode_ilp: index entry off the stores' path
-            KernelFn pfn = select_ilp_kernel(p.g.itemsize, swap);
-            if (!pfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t igrid = p.n_units > p.n_idx ? p.n_units : p.n_idx;
-            if (igrid == 0) return ZHIP_OK;
-            g_last_kernel = "k_decode_ilp";
-            hipLaunchKernelGGL(pfn, dim3(igrid), dim3(kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        if (il && g_tune_arm == 25) {  // k_decode_ilc: tables built in LDS, predicted loads first
-            KernelFn cfn = select_ilc_kernel(p.g.itemsize, swap);
-            if (!cfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t igrid = p.n_units > p.n_idx ? p.n_units : p.n_idx;
-            if (igrid == 0) return ZHIP_OK;
-            g_last_kernel = "k_decode_ilc";
-            hipLaunchKernelGGL(cfn, dim3(igrid), dim3(kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        if (il && g_tune_arm >= 20 && g_tune_arm <= 24) {
-            // k_decode_ilq arms: NQ units per workgroup, tables by registers or LDS-DMA
-            static const char* names[] = {"k_decode_ilq2", "k_decode_ilq4", "k_decode_ilq1_glds",
-                                          "k_decode_ilq2_glds", "k_decode_ilq4_glds"};
-            const int a = g_tune_arm - 20;
-            const int nq = (a == 0 || a == 3) ? 2 : (a == 1 || a == 4) ? 4 : 1;
-            if (p.nseg % (uint32_t)nq) return ZHIP_E_UNSUPPORTED;
-            KernelFn qfn = select_ilq_kernel(p.g.itemsize, swap, nq, a >= 2);
-            if (!qfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t ug = (uint32_t)(((uint64_t)p.n_units + nq - 1u) / nq);
-            const uint32_t xg = (p.n_idx + (uint32_t)nq - 1u) / (uint32_t)nq;
-            const uint32_t qgrid = ug > xg ? ug : xg;
-            if (qgrid == 0) return ZHIP_OK;
-            g_last_kernel = names[a];
-            hipLaunchKernelGGL(qfn, dim3(qgrid), dim3(nq * kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-#endif
-        // grids of at most kIlwMaxUnits units (2 per CU: the N = 4 / 8 shares of
-        // the strong-scaled headline) with fewer chunks than CUs: half units of
-        // 16 KiB (k_decode_ilh, two workgroups per unit) publishing through the
-        // look-back finalizer -- graph-timed 8.39 vs 9.77 us (k_decode_ilw512)
-        // at the N = 8 share, 10.73 vs 11.03 at N = 4 (profiles/r06/a/).
-        // (Tuning build: arm 0 only; arm 58 / 49 keep k_decode_ilw512.)
-        if (il && p.ilh_klane && p.n_units <= kIlwMaxUnits && lb_ok && p.nseg <= 32u &&
-            (g_tune_arm == 0 || g_tune_arm == 60) && (tune & ~kTuneStamp) == 0) {
-            KernelFn hfn = select_ilh_kernel(p.g.itemsize, swap, true, p.aff_ok != 0);
-            if (!hfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t hunits = 2u * p.n_units;
-            const uint32_t hgrid = hunits > p.n_idx ? hunits : p.n_idx;
-            if (hgrid == 0) return ZHIP_OK;
-            g_last_kernel = "k_decode_ilh";
-            hipLaunchKernelGGL(hfn, dim3(hgrid), dim3(kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        // otherwise 512 lanes per unit, four blocks per lane (k_decode_ilw,
-        // decode_rows.hip) -- graph-timed 8.8 vs 9.4 us at the N = 8 share, 10.3
-        // vs 11.0 at N = 4; 14.6 vs 16.5 for k_decode_il at N = 2
-        // (profiles/r05/f/).  (Tuning build: any arm keeps k_decode_il.)
-        if (il && p.ilw_nt == 512u && p.n_units <= kIlwMaxUnits &&
-            (g_tune_arm == 0 || g_tune_arm == 45 || g_tune_arm == 61 || ((g_tune_arm == 49 || g_tune_arm == 58) && p.aff_ok)) &&
-            (tune & ~kTuneStamp) == 0) {
-            // (tuning arms, whole-chunk reads: 49 the split publication, 58 the
-            // look-back finalizer)
-            const int nt = g_tune_arm == 49 ? 515 : (g_tune_arm == 58 && lb_ok && p.nseg <= 64u) ? 516 : 512;
-            KernelFn wfn = select_ilw_kernel(p.g.itemsize, swap, nt, false, p.aff_ok != 0);
-            if (!wfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t wgrid = p.n_units > p.n_idx ? p.n_units : p.n_idx;
-            if (wgrid == 0) return ZHIP_OK;
-            g_last_kernel = "k_decode_ilw512";
-            hipLaunchKernelGGL(wfn, dim3(wgrid), dim3(512), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        if (il) {
-#if ZHIP_TUNING
-            // (arms 1 / 2 are k_decode_il's own; every other arm keeps production here)
-            // (58: the look-back finalizer, while fewer chunks than CUs)
-            KernelFn ifn = (g_tune_arm == 1 || g_tune_arm == 2 ||
-                            ((g_tune_arm == 49 || (g_tune_arm >= 51 && g_tune_arm <= 57) ||
-                              (g_tune_arm == 58 && lb_ok && p.nseg <= 32u) ||
-                              g_tune_arm == 64 || g_tune_arm == 65) && p.aff_ok))
-                               ? select_il_kernel_arm(crc, p.g.itemsize, swap, g_tune_arm)
-                           : (tune & kTuneCfLookup) ? select_il_kernel_cf(crc, p.g.itemsize, swap)
-                           : (tune & kTuneIlLean) ? select_il_kernel_lean(crc, p.g.itemsize, swap)
-                           : (tune & (kTuneIlRegMul | kTuneIlOcc6))
-                               ? select_il_kernel_regmul(crc, p.g.itemsize, swap, (tune & kTuneIlOcc6) != 0)
-                               : (tune & (kTuneNoTables | kTuneNoRunEnd | kTuneNoPub | kTuneStamp))
-                                   ? select_il_kernel_tuned(crc, p.g.itemsize, swap)
-                                   : select_il_kernel(crc, p.g.itemsize, swap, p.aff_ok != 0);
-#else
-            KernelFn ifn = select_il_kernel(crc, p.g.itemsize, swap, p.aff_ok != 0);
-#endif
-            if (!ifn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t igrid = p.n_units > p.n_idx ? p.n_units : p.n_idx;
-            if (igrid == 0) return ZHIP_OK;
-            g_last_kernel = "k_decode_il";
-            hipLaunchKernelGGL(ifn, dim3(igrid), dim3(kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-#if ZHIP_TUNING
-        KernelFn fn = nu != 2 ? nullptr
-                      : (tune & kTuneTrailingCrc) ? select_pair_kernel(crc, p.g.itemsize, swap, 3)
-                      : (tune & kTuneSplitChain) ? select_pair_kernel(crc, p.g.itemsize, swap, 4)
-                      : (tune & kTuneSkipCrc) ? select_pair_kernel(crc, p.g.itemsize, swap, 5)
-                      : (tune & (kTunePrio | kTuneDeferB))
-                          ? select_pair_kernel(crc, p.g.itemsize, swap,
-                                               (tune & kTunePrio) && (tune & kTuneDeferB) ? 8
-                                               : (tune & kTunePrio) ? 6 : 7)
-                          : nullptr;
-#else
-        KernelFn fn = nullptr;
-#endif
-        if (!fn) fn = select_pair_kernel(crc, p.g.itemsize, swap, nu);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        // chunks of more than 32 units (> 1 MiB): one unit per 256-thread half of
-        // a 512-thread workgroup (k_decode_duo; C1 0.55 -> 0.62 of HBM peak,
-        // profiles/r02/kernel_arms_ab.jsonl); kTuneDuo forces it
-        if ((tune & kTuneDuo) || (p.nseg > 32 && !(tune & (kTuneSingle | kTuneSkipCrc)))) {
-            KernelFn dfn = select_duo_kernel(crc, p.g.itemsize, swap);
-            if (!dfn) return ZHIP_E_UNSUPPORTED;
-            const uint32_t duos = (uint32_t)(((uint64_t)p.n_units + 1u) / 2u);
-            const uint32_t dgrid = duos > p.n_idx ? duos : p.n_idx;
-            if (dgrid == 0) return ZHIP_OK;
-            g_last_kernel = "k_decode_duo";
-            hipLaunchKernelGGL(dfn, dim3(dgrid), dim3(2 * kThreads), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-        const uint32_t pairs = (uint32_t)(((uint64_t)p.n_units + nu - 1u) / nu);
-        const uint32_t grid = pairs > p.n_idx ? pairs : p.n_idx;
-        if (grid == 0) return ZHIP_OK;
-        // one resident wave of workgroups (4 per CU; max_grid = 8 per CU): the
-        // workgroups of one XCD take a contiguous eighth of the batch
-        DecodeParams q = p;
-        q.xcd_run = (nu == 2 && !(tune & kTuneNoXcd) && grid % 8u == 0u &&
-                     grid <= (uint32_t)(max_grid / 8) * 4u) ? grid / 8u : 0u;
-        q.h.xcd_run = q.xcd_run;
-        q.h.d_xcd = make_fdiv(q.xcd_run ? q.xcd_run : 1u);
-        g_last_kernel = "k_decode_pair";
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), 0, stream, q);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    if (p.rows) {
-        KernelFn fn = select_rows_kernel((p.lflags & ZHIP_LF_CRC) != 0, p.g.itemsize, (p.lflags & ZHIP_LF_SWAP) != 0,
-                                         (int)(p.seg / kWgStride));
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_units == 0) return ZHIP_OK;
-        if (g_tune_max_grid <= 0) {
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), kThreads,
-                                                             0) == hipSuccess && per_cu > 0)
-                max_grid = (max_grid / 8) * per_cu;
-        }
-        const uint32_t grid = p.n_units < (uint32_t)max_grid ? p.n_units : (uint32_t)max_grid;
-        g_last_kernel = "k_decode_rows";
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    if (p.tq >= 0 && p.tile4) {
-        // four tiles per workgroup, non-persistent (k_decode_tile4, decode_tile.hip)
-        // (arm kTuneTile4F: one A_64 chain per thread when the layout's tile step is
-        // 256 B, k_decode_tile4f -- exact, measured 0.3-0.4 us slower on C3)
-        const bool f4 = ZHIP_TUNING && p.t4f_tab != nullptr && (p.lflags & ZHIP_LF_CRC) != 0;
-        const bool w4 = !f4 && p.t4w_tab != nullptr && (p.lflags & ZHIP_LF_CRC) != 0;
-        const bool swp = (p.lflags & ZHIP_LF_SWAP) != 0;
-        // two tiles per workgroup (2 048 workgroups on C3: two residency rounds
-        // instead of one) -- graph-timed 27.8-27.9 vs 28.4-30.0 us on C3
-        // (profiles/r05/l/); tuning arm 38 keeps four, 37 takes one (46 us)
-        if (w4 && ((p.t2w_kq && g_tune_arm != 38 && g_tune_arm != 37) || (g_tune_arm == 37 && p.t1w_kq))) {
-            const int nt = g_tune_arm == 37 ? 1 : 2;
-            // (tuning arm 49: the split publication of 17..32 workgroups per chunk)
-            // (tuning arm 67: the byte-table chains, where the plan built them)
-            KernelFn fn2 = select_tile2w_kernel(p.g.itemsize, swp,
-                                                (nt == 2 && g_tune_arm == 49) ? 3
-                                                : (nt == 2 && g_tune_arm == 67 && p.tbt_tab) ? 4 : nt);
-            if (!fn2) return ZHIP_E_UNSUPPORTED;
-            if (p.n_units == 0) return ZHIP_OK;
-            DecodeParams q = p;
-            q.t4w_kq = nt == 1 ? p.t1w_kq : p.t2w_kq;
-            g_last_kernel = nt == 1 ? "k_decode_tile1w" : g_tune_arm == 49 ? "k_decode_tile2ws"
-                            : (g_tune_arm == 67 && p.tbt_tab) ? "k_decode_tile2w_bt" : "k_decode_tile2w";
-            hipLaunchKernelGGL(fn2, dim3(p.n_units / (uint32_t)nt), dim3(kThreads), 0, stream, q);
-            return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-        }
-#if ZHIP_TUNING
-        KernelFn fn = f4 ? select_tile4f_kernel(p.g.itemsize, swp)
-                      : w4 ? select_tile4w_kernel(p.g.itemsize, swp)
-                           : select_tile4_kernel((p.lflags & ZHIP_LF_CRC) != 0, p.g.itemsize, swp);
-#else
-        KernelFn fn = w4 ? select_tile4w_kernel(p.g.itemsize, swp)
-                         : select_tile4_kernel((p.lflags & ZHIP_LF_CRC) != 0, p.g.itemsize, swp);
-#endif
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_units == 0) return ZHIP_OK;
-        g_last_kernel = f4 ? "k_decode_tile4f" : w4 ? "k_decode_tile4w" : "k_decode_tile4";
-        hipLaunchKernelGGL(fn, dim3(p.n_units / 4u), dim3(kThreads), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    if (p.tq >= 0 && p.tile2) {
-        // consecutive tile pairs (k_decode_tile4w<2>, decode_tile.hip): 128^3
-        // chunks' two 256-byte column blocks of one row band per workgroup
-        KernelFn fn = select_tile2w_kernel(p.g.itemsize, (p.lflags & ZHIP_LF_SWAP) != 0, 2);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_units == 0) return ZHIP_OK;
-        if (p.n_units / 2u >= (1u << 31)) return ZHIP_E_UNSUPPORTED;
-        g_last_kernel = "k_decode_tilep";
-        hipLaunchKernelGGL(fn, dim3(p.n_units / 2u), dim3(kThreads), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    if (p.tq >= 0 && p.tileg) {
-        // tiles grouped by four along a stored dim (k_decode_tileg, decode_tile.hip)
-        // (k_decode_tilegw when the plan's wave-per-tile chains are selected)
-        const bool gw = p.t4w_tab != nullptr && (p.lflags & ZHIP_LF_CRC) != 0;
-        // (arm 2: the returning publication whatever the flags)
-        const bool defer = p.defer != 0 && g_tune_arm != 2;
-        // two tiles per workgroup where the plan built their constants (as
-        // k_decode_tile4w); tuning arms 38 (deferred) / 2 (returning) keep four
-        int nt = (gw && p.t2w_kq && g_tune_arm != 38 && g_tune_arm != 2 && g_tune_arm != 40) ? 2 : 4;
-        int nsel = nt;
-#if ZHIP_TUNING
-        if (gw && g_tune_arm == 40 && p.tglt_kq) nt = nsel = 5;  // four tiles, lanes pick the tile
-        if (nt == 2 && g_tune_arm == 48) nsel = 6;  // the arrival words packed (round-4 layout)
-        // the look-back finalizer (fewer chunks than CUs; the spread subwords)
-        if (nt == 2 && g_tune_arm == 62 && lb_ok && p.n_groups <= 128u) nsel = 7;
-        if (nt == 2 && g_tune_arm == 66 && p.tbt_tab) nsel = 8;  // the byte-table chains
-#endif
-        KernelFn fn = gw ? select_tilegw_kernel(p.g.itemsize, (p.lflags & ZHIP_LF_SWAP) != 0, defer, nsel)
-                         : select_tileg_kernel((p.lflags & ZHIP_LF_CRC) != 0, p.g.itemsize,
-                                               (p.lflags & ZHIP_LF_SWAP) != 0, defer);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_chunks == 0) return ZHIP_OK;
-        const uint64_t ggrid = (uint64_t)p.n_chunks * p.n_groups * (uint32_t)(nt == 2 ? 2 : 1);
-        if (ggrid >= (1ull << 31)) return ZHIP_E_UNSUPPORTED;
-        DecodeParams q = p;
-        if (nt == 2) q.t4w_kq = p.t2w_kq;
-        if (nt == 5) q.t4w_kq = p.tglt_kq;
-        g_last_kernel = !gw ? "k_decode_tileg" : nsel == 6 ? "k_decode_tileg2wp" : nsel == 7 ? "k_decode_tileg2w_lb"
-                                           : nsel == 8 ? "k_decode_tileg2w_bt"
-                                           : nt == 2 ? "k_decode_tileg2w"
-                                           : nt == 5 ? "k_decode_tileglt"
-                                                                                      : "k_decode_tilegw";
-        hipLaunchKernelGGL(fn, dim3((uint32_t)ggrid), dim3(kThreads), 0, stream, q);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    if (p.tq >= 0) {
-        KernelFn fn = select_tile_kernel((p.lflags & ZHIP_LF_CRC) != 0, p.g.itemsize, (p.lflags & ZHIP_LF_SWAP) != 0);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_units == 0) return ZHIP_OK;
-        if (g_tune_max_grid <= 0) {
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), kThreads,
-                                                             0) == hipSuccess && per_cu > 0)
-                max_grid = (max_grid / 8) * per_cu;
-        }
-        const uint32_t grid = p.n_units < (uint32_t)max_grid ? p.n_units : (uint32_t)max_grid;
-        g_last_kernel = "k_decode_tile";
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    KernelFn fn = select_decode_kernel((p.lflags & ZHIP_LF_CRC) != 0, (p.lflags & ZHIP_LF_NO_WRITE) == 0,
-                                       p.fast != 0, p.g.itemsize, (p.lflags & ZHIP_LF_SWAP) != 0,
-                                       (int)(p.seg / kWgStride));
-    if (!fn) return ZHIP_E_UNSUPPORTED;
-    if (p.n_units == 0) return ZHIP_OK;
-    if (g_tune_max_grid <= 0) {
-        // persistent grid = resident workgroups (units are software-pipelined per WG)
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn),
-                                                         kThreads, 0) == hipSuccess && per_cu > 0)
-            max_grid = (max_grid / 8) * per_cu;  // max_grid arrives as CUs * 8
-    }
-    const uint32_t grid = p.n_units < (uint32_t)max_grid ? p.n_units : (uint32_t)max_grid;
-    g_last_kernel = "k_decode";
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
+        (!(L.tune & kTunePersist) || lead_launch))
+        return launch_row_units(L);
+    if (p.rows)
+        return launch_persistent(L, select_rows_kernel(crc, L.item, L.swap, (int)(p.seg / kWgStride)), "k_decode_rows");
+    if (p.tq >= 0 && p.tile4) return launch_tile4(L);
+    if (p.tq >= 0 && p.tile2) return launch_tile_pairs(L);
+    if (p.tq >= 0 && p.tileg) return launch_tile_groups(L);
+    if (p.tq >= 0) return launch_persistent(L, select_tile_kernel(crc, L.item, L.swap), "k_decode_tile");
+    return launch_persistent(L, select_decode_kernel(crc, (p.lflags & ZHIP_LF_NO_WRITE) == 0, p.fast != 0, L.item,
+                                                     L.swap, (int)(p.seg / kWgStride)), "k_decode");
 }
 
 }  // namespace zhip

@@ -21,6 +21,7 @@
 #include "../../include/zarrhip.h"
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
+#include "zhip_dispatch.h"
 #include "zhip_device.h"
 #include "zhip_decode_common.h"
 
@@ -1077,64 +1078,41 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
                                hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 
-using KernelFn = void (*)(const DecodeParams);
-
 template <int NU>
 KernelFn select_pair_nu(bool crc, int item, bool swap) {
-    switch (item) {
-        case 1: return crc ? k_decode_pair<true, 1, false, NU> : k_decode_pair<false, 1, false, NU>;
-        case 2: return crc ? (swap ? k_decode_pair<true, 2, true, NU> : k_decode_pair<true, 2, false, NU>)
-                           : (swap ? k_decode_pair<false, 2, true, NU> : k_decode_pair<false, 2, false, NU>);
-        case 4: return crc ? (swap ? k_decode_pair<true, 4, true, NU> : k_decode_pair<true, 4, false, NU>)
-                           : (swap ? k_decode_pair<false, 4, true, NU> : k_decode_pair<false, 4, false, NU>);
-        case 8: return crc ? (swap ? k_decode_pair<true, 8, true, NU> : k_decode_pair<true, 8, false, NU>)
-                           : (swap ? k_decode_pair<false, 8, true, NU> : k_decode_pair<false, 8, false, NU>);
-        default: return nullptr;
-    }
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        return crc ? k_decode_pair<true, T::item, T::swap, NU> : k_decode_pair<false, T::item, T::swap, NU>;
+    });
 }
 
-KernelFn select_pair_kernel(bool crc, int item, bool swap, int nu) {
-    if (nu == 9) {  // no data CRC, leading index-check workgroups (k_decode_lead)
+KernelFn select_pair_kernel(bool crc, int item, bool swap, PairForm form) {
+    if (form == kPairLead) {  // no data CRC, leading index-check workgroups (k_decode_lead)
         if (crc) return nullptr;
-        switch (item) {
-            case 1: return k_decode_lead<1, false>;
-            case 2: return swap ? k_decode_lead<2, true> : k_decode_lead<2, false>;
-            case 4: return swap ? k_decode_lead<4, true> : k_decode_lead<4, false>;
-            case 8: return swap ? k_decode_lead<8, true> : k_decode_lead<8, false>;
-            default: return nullptr;
-        }
+        return for_item(item, swap, [](auto t) -> KernelFn {
+            return k_decode_lead<decltype(t)::item, decltype(t)::swap>;
+        });
     }
-    if (nu == 10 || nu == 11) {  // chunks of <= 16 / 8 KiB: four / eight per workgroup (k_decode_lead4)
-        const bool e8 = nu == 11;
-        switch (item) {
-            case 1: return crc ? (e8 ? k_decode_lead4<1, false, true, 8> : k_decode_lead4<1, false, true>)
-                               : (e8 ? k_decode_lead4<1, false, false, 8> : k_decode_lead4<1, false>);
-            case 2: return crc ? (swap ? (e8 ? k_decode_lead4<2, true, true, 8> : k_decode_lead4<2, true, true>)
-                                       : (e8 ? k_decode_lead4<2, false, true, 8> : k_decode_lead4<2, false, true>))
-                               : (swap ? (e8 ? k_decode_lead4<2, true, false, 8> : k_decode_lead4<2, true>)
-                                       : (e8 ? k_decode_lead4<2, false, false, 8> : k_decode_lead4<2, false>));
-            case 4: return crc ? (swap ? (e8 ? k_decode_lead4<4, true, true, 8> : k_decode_lead4<4, true, true>)
-                                       : (e8 ? k_decode_lead4<4, false, true, 8> : k_decode_lead4<4, false, true>))
-                               : (swap ? (e8 ? k_decode_lead4<4, true, false, 8> : k_decode_lead4<4, true>)
-                                       : (e8 ? k_decode_lead4<4, false, false, 8> : k_decode_lead4<4, false>));
-            case 8: return crc ? (swap ? (e8 ? k_decode_lead4<8, true, true, 8> : k_decode_lead4<8, true, true>)
-                                       : (e8 ? k_decode_lead4<8, false, true, 8> : k_decode_lead4<8, false, true>))
-                               : (swap ? (e8 ? k_decode_lead4<8, true, false, 8> : k_decode_lead4<8, true>)
-                                       : (e8 ? k_decode_lead4<8, false, false, 8> : k_decode_lead4<8, false>));
-            default: return nullptr;
-        }
+    if (form == kPairLead4 || form == kPairLead8) {  // chunks of <= 16 / 8 KiB: four / eight per workgroup
+        const bool e8 = form == kPairLead8;
+        return for_item(item, swap, [&](auto t) -> KernelFn {
+            using T = decltype(t);
+            return crc ? (e8 ? k_decode_lead4<T::item, T::swap, true, 8> : k_decode_lead4<T::item, T::swap, true>)
+                       : (e8 ? k_decode_lead4<T::item, T::swap, false, 8> : k_decode_lead4<T::item, T::swap>);
+        });
     }
 #if ZHIP_TUNING
-    if (nu == 5)  // tuning arm (headline item type only): VARIANT 3, no lookups
-        return !(crc && item == 4 && !swap) ? nullptr : k_decode_pair<true, 4, false, 2, 8, 3>;
-    if (nu >= 6 && nu <= 8) {  // tuning arms (headline item type only): VARIANT 6 / 7 / 8
-        if (!(crc && item == 4 && !swap)) return nullptr;
-        return nu == 6 ? k_decode_pair<true, 4, false, 2, 8, 6>
-               : nu == 7 ? k_decode_pair<true, 4, false, 2, 8, 7> : k_decode_pair<true, 4, false, 2, 8, 8>;
+    if (form == kPairNoLookups)  // tuning arm (headline item type only): VARIANT 3, no lookups
+        return !headline_item(crc, item, swap) ? nullptr : k_decode_pair<true, 4, false, 2, 8, 3>;
+    if (form == kPairPrio || form == kPairDeferB || form == kPairPrioDeferB) {
+        // tuning arms (headline item type only): VARIANT 6 / 7 / 8
+        if (!headline_item(crc, item, swap)) return nullptr;
+        return form == kPairPrio ? k_decode_pair<true, 4, false, 2, 8, 6>
+               : form == kPairDeferB ? k_decode_pair<true, 4, false, 2, 8, 7> : k_decode_pair<true, 4, false, 2, 8, 8>;
     }
-    if (nu == 1) return select_pair_nu<1>(crc, item, swap);  // kTuneSingle
+    if (form == kPairSingle) return select_pair_nu<1>(crc, item, swap);  // kTuneSingle
 #endif
-    if (nu != 2) return nullptr;
+    if (form != kPairTwo) return nullptr;
     return select_pair_nu<2>(crc, item, swap);
 }
 
@@ -1635,25 +1613,25 @@ void k_decode_il(const DecodeParams p) {
 
 #if ZHIP_TUNING
 KernelFn select_il_kernel_tuned(bool crc, int item, bool swap) {  // runtime timing arms (p.tune)
-    return (crc && item == 4 && !swap) ? k_decode_il<true, 4, false, false, false, 0, true> : nullptr;
+    return headline_item(crc, item, swap) ? k_decode_il<true, 4, false, false, false, 0, true> : nullptr;
 }
 
 KernelFn select_il_kernel_arm(bool crc, int item, bool swap, int arm) {  // ZHIP_TUNE_ARM experiments
-    if (!(crc && item == 4 && !swap)) return nullptr;
+    if (!headline_item(crc, item, swap)) return nullptr;
     switch (arm) {
-        case 1: return k_decode_il<true, 4, false, false, false, 0, false, 0>;  // round 3: words 16 B apart
-        case 2: return k_decode_il<true, 4, false, false, false, 0, false, 2>;  // deferred verdicts
-        case 49: return k_decode_il<true, 4, false, false, false, 0, false, 4, true>;  // split publication (AFF)
-        case 51: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 1>;  // priority: run end (AFF)
-        case 52: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 2>;  // priority: load issue (AFF)
-        case 53: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 3>;  // priority: both (AFF)
-        case 54: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 4>;  // priority: to the tables (AFF; production)
-        case 56: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 0>;  // no priority (AFF; round-5 production)
-        case 57: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 12>;  // 54 + XCD eighths (AFF)
-        case 55: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 5>;  // 54 + run end (AFF)
-        case 58: return k_decode_il<true, 4, false, false, false, 0, false, 5, true, 4>;  // 54 + look-back finalizer (AFF)
-        case 64: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 4, 1>;  // 54 + write-through stores
-        case 65: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 4, 2>;  // 54 + buffer nt stores
+        case kArmPub16: return k_decode_il<true, 4, false, false, false, 0, false, 0>;  // round 3: words 16 B apart
+        case kArmDeferred: return k_decode_il<true, 4, false, false, false, 0, false, 2>;  // deferred verdicts
+        case kArmSplitPub: return k_decode_il<true, 4, false, false, false, 0, false, 4, true>;  // split publication (AFF)
+        case kArmIlPrioRunEnd: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 1>;  // priority: run end (AFF)
+        case kArmIlPrioLoads: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 2>;  // priority: load issue (AFF)
+        case kArmIlPrioBoth: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 3>;  // priority: both (AFF)
+        case kArmIlPrioTables: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 4>;  // priority: to the tables (AFF; production)
+        case kArmIlNoPrio: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 0>;  // no priority (AFF; round-5 production)
+        case kArmIlXcd: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 12>;  // 54 + XCD eighths (AFF)
+        case kArmIlPrioTablesEnd: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 5>;  // 54 + run end (AFF)
+        case kArmLookBack: return k_decode_il<true, 4, false, false, false, 0, false, 5, true, 4>;  // 54 + look-back finalizer (AFF)
+        case kArmIlStoreWt: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 4, 1>;  // 54 + write-through stores
+        case kArmIlStoreNt: return k_decode_il<true, 4, false, false, false, 0, false, 3, true, 4, 2>;  // 54 + buffer nt stores
         default: return k_decode_il<true, 4, false>;  // arms of other kernels: production
     }
 }
@@ -1687,33 +1665,27 @@ int launch_dv_check(const zhip_dv_ref* d_refs, uint32_t n_refs, hipStream_t stre
 
 #if ZHIP_TUNING
 KernelFn select_il_kernel_lean(bool crc, int item, bool swap) {  // kTuneIlLean (4-byte LE CRC item type only)
-    return (crc && item == 4 && !swap) ? k_decode_il<true, 4, false, true> : nullptr;
+    return headline_item(crc, item, swap) ? k_decode_il<true, 4, false, true> : nullptr;
 }
 
 KernelFn select_il_kernel_cf(bool crc, int item, bool swap) {  // kTuneCfLookup timing arm (results invalid)
-    return (crc && item == 4 && !swap) ? k_decode_il<true, 4, false, false, true> : nullptr;
+    return headline_item(crc, item, swap) ? k_decode_il<true, 4, false, false, true> : nullptr;
 }
 
 KernelFn select_il_kernel_regmul(bool crc, int item, bool swap, bool occ6) {  // kTuneIlRegMul / kTuneIlOcc6 arms
-    if (!(crc && item == 4 && !swap)) return nullptr;
+    if (!headline_item(crc, item, swap)) return nullptr;
     return occ6 ? k_decode_il<true, 4, false, false, false, 2> : k_decode_il<true, 4, false, false, false, 1>;
 }
 
 #endif
 
 KernelFn select_il_kernel(bool crc, int item, bool swap, bool aff) {  // aff: ZHIP_DF_WHOLE (CRC chains)
-#define ZHIP_IL(I, W) (aff ? k_decode_il<true, I, W, false, false, 0, false, 3, true, 4> : k_decode_il<true, I, W>)
-    switch (item) {
-        case 1: return crc ? ZHIP_IL(1, false) : k_decode_il<false, 1, false>;
-        case 2: return crc ? (swap ? ZHIP_IL(2, true) : ZHIP_IL(2, false))
-                           : (swap ? k_decode_il<false, 2, true> : k_decode_il<false, 2, false>);
-        case 4: return crc ? (swap ? ZHIP_IL(4, true) : ZHIP_IL(4, false))
-                           : (swap ? k_decode_il<false, 4, true> : k_decode_il<false, 4, false>);
-        case 8: return crc ? (swap ? ZHIP_IL(8, true) : ZHIP_IL(8, false))
-                           : (swap ? k_decode_il<false, 8, true> : k_decode_il<false, 8, false>);
-        default: return nullptr;
-    }
-#undef ZHIP_IL
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        if (!crc) return k_decode_il<false, T::item, T::swap>;
+        return aff ? k_decode_il<true, T::item, T::swap, false, false, 0, false, 3, true, 4>
+                   : k_decode_il<true, T::item, T::swap>;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2362,20 +2334,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
 // AFF form for ZHIP_DF_WHOLE launches; the tuning build adds the returning
 // publication (arm 41) and LB without AFF (arm 59)
 KernelFn select_ilh_kernel(int item, bool swap, bool lb, bool aff) {  // CRC chains only
+    if (!ZHIP_TUNING && !lb) return nullptr;
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
 #if ZHIP_TUNING
-#define ZHIP_ILH(I, W) (!lb ? k_decode_ilh<I, W> : aff ? k_decode_ilh<I, W, true, true> : k_decode_ilh<I, W, true>)
-#else
-    if (!lb) return nullptr;
-#define ZHIP_ILH(I, W) (aff ? k_decode_ilh<I, W, true, true> : k_decode_ilh<I, W, true>)
+        if (!lb) return k_decode_ilh<T::item, T::swap>;
 #endif
-    switch (item) {
-        case 1: return ZHIP_ILH(1, false);
-        case 2: return swap ? ZHIP_ILH(2, true) : ZHIP_ILH(2, false);
-        case 4: return swap ? ZHIP_ILH(4, true) : ZHIP_ILH(4, false);
-        case 8: return swap ? ZHIP_ILH(8, true) : ZHIP_ILH(8, false);
-        default: return nullptr;
-    }
-#undef ZHIP_ILH
+        return aff ? k_decode_ilh<T::item, T::swap, true, true> : k_decode_ilh<T::item, T::swap, true>;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2544,64 +2510,43 @@ __global__ __launch_bounds__(NT) void k_decode_ilw(const DecodeParams p) {
 
 // production: 512 lanes, the LDS lane multiply (small grids, launch_decode),
 // the AFF form for ZHIP_DF_WHOLE launches; the tuning build adds 1024 lanes
-// and the register multiply (513: half the waves, arm 42)
-KernelFn select_ilw_kernel(int item, bool swap, int nt, bool lmr, bool aff) {  // CRC chains only
+// and the register multiply (kIlw512Half: half the waves, arm 42)
+KernelFn select_ilw_kernel(int item, bool swap, IlwForm form, bool lmr, bool aff) {  // CRC chains only
+    if (!ZHIP_TUNING && (form != kIlw512 || lmr)) return nullptr;
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
 #if ZHIP_TUNING
-#define ZHIP_ILW(I, W)                                                                         \
-    (nt == 1024 ? (lmr ? k_decode_ilw<I, W, 1024, true> : k_decode_ilw<I, W, 1024>)            \
-     : nt == 513 ? k_decode_ilw<I, W, 512, false, true>                                         \
-     : nt == 515 ? k_decode_ilw<I, W, 512, false, false, true, true>                            \
-     : nt == 516 ? k_decode_ilw<I, W, 512, false, false, true, false, true>                     \
-     : lmr       ? k_decode_ilw<I, W, 512, true>                                                \
-     : aff       ? k_decode_ilw<I, W, 512, false, false, true>                                  \
-                 : k_decode_ilw<I, W, 512>)
-#else
-    if (nt != 512 || lmr) return nullptr;
-#define ZHIP_ILW(I, W) (aff ? k_decode_ilw<I, W, 512, false, false, true> : k_decode_ilw<I, W, 512>)
+        if (form == kIlw1024)
+            return lmr ? k_decode_ilw<T::item, T::swap, 1024, true> : k_decode_ilw<T::item, T::swap, 1024>;
+        if (form == kIlw512Half) return k_decode_ilw<T::item, T::swap, 512, false, true>;
+        if (form == kIlw512Split) return k_decode_ilw<T::item, T::swap, 512, false, false, true, true>;
+        if (form == kIlw512LookBack) return k_decode_ilw<T::item, T::swap, 512, false, false, true, false, true>;
+        if (lmr) return k_decode_ilw<T::item, T::swap, 512, true>;
 #endif
-    switch (item) {
-        case 1: return ZHIP_ILW(1, false);
-        case 2: return swap ? ZHIP_ILW(2, true) : ZHIP_ILW(2, false);
-        case 4: return swap ? ZHIP_ILW(4, true) : ZHIP_ILW(4, false);
-        case 8: return swap ? ZHIP_ILW(8, true) : ZHIP_ILW(8, false);
-        default: return nullptr;
-    }
-#undef ZHIP_ILW
+        return aff ? k_decode_ilw<T::item, T::swap, 512, false, false, true> : k_decode_ilw<T::item, T::swap, 512>;
+    });
 }
 
 #if ZHIP_TUNING
 KernelFn select_ilp_kernel(int item, bool swap) {  // CRC chains only
-    switch (item) {
-        case 1: return k_decode_ilp<1, false>;
-        case 2: return swap ? k_decode_ilp<2, true> : k_decode_ilp<2, false>;
-        case 4: return swap ? k_decode_ilp<4, true> : k_decode_ilp<4, false>;
-        case 8: return swap ? k_decode_ilp<8, true> : k_decode_ilp<8, false>;
-        default: return nullptr;
-    }
+    return for_item(item, swap, [](auto t) -> KernelFn { return k_decode_ilp<decltype(t)::item, decltype(t)::swap>; });
 }
 
 KernelFn select_ilc_kernel(int item, bool swap) {  // CRC chains only
-    switch (item) {
-        case 1: return k_decode_ilc<1, false>;
-        case 2: return swap ? k_decode_ilc<2, true> : k_decode_ilc<2, false>;
-        case 4: return swap ? k_decode_ilc<4, true> : k_decode_ilc<4, false>;
-        case 8: return swap ? k_decode_ilc<8, true> : k_decode_ilc<8, false>;
-        default: return nullptr;
-    }
+    return for_item(item, swap, [](auto t) -> KernelFn { return k_decode_ilc<decltype(t)::item, decltype(t)::swap>; });
 }
 #endif
 
 #if ZHIP_TUNING
 KernelFn select_ilq_kernel(int item, bool swap, int nq, bool glds) {  // CRC chains only
-#define ZHIP_ILQ(I, W) \
-    (nq == 4 ? (glds ? k_decode_ilq<I, W, 4, true> : k_decode_ilq<I, W, 4, false>) \
-             : nq == 2 ? (glds ? k_decode_ilq<I, W, 2, true> : k_decode_ilq<I, W, 2, false>) \
-                       : (glds ? k_decode_ilq<I, W, 1, true> : k_decode_ilq<I, W, 1, false>))
-    switch (item) {
-        case 4: return swap ? ZHIP_ILQ(4, true) : ZHIP_ILQ(4, false);
-        default: return nullptr;
-    }
-#undef ZHIP_ILQ
+    if (item != 4) return nullptr;  // 4-byte items only
+    auto pick = [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        return nq == 4 ? (glds ? k_decode_ilq<T::item, T::swap, 4, true> : k_decode_ilq<T::item, T::swap, 4, false>)
+               : nq == 2 ? (glds ? k_decode_ilq<T::item, T::swap, 2, true> : k_decode_ilq<T::item, T::swap, 2, false>)
+                         : (glds ? k_decode_ilq<T::item, T::swap, 1, true> : k_decode_ilq<T::item, T::swap, 1, false>);
+    };
+    return swap ? pick(ItemTag<4, true>{}) : pick(ItemTag<4, false>{});
 }
 #endif
 
@@ -2751,47 +2696,30 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
 #if ZHIP_TUNING
 KernelFn select_xw_kernel(bool crc, int item, bool swap) {
     if (!crc) return nullptr;
-    switch (item) {
-        case 1: return k_decode_xw<true, 1, false>;
-        case 2: return swap ? k_decode_xw<true, 2, true> : k_decode_xw<true, 2, false>;
-        case 4: return swap ? k_decode_xw<true, 4, true> : k_decode_xw<true, 4, false>;
-        case 8: return swap ? k_decode_xw<true, 8, true> : k_decode_xw<true, 8, false>;
-        default: return nullptr;
-    }
+    return for_item(item, swap, [](auto t) -> KernelFn {
+        return k_decode_xw<true, decltype(t)::item, decltype(t)::swap>;
+    });
 }
 #endif
 
 KernelFn select_duo_kernel(bool crc, int item, bool swap) {
-    switch (item) {
-        case 1: return crc ? k_decode_duo<true, 1, false> : k_decode_duo<false, 1, false>;
-        case 2: return crc ? (swap ? k_decode_duo<true, 2, true> : k_decode_duo<true, 2, false>)
-                           : (swap ? k_decode_duo<false, 2, true> : k_decode_duo<false, 2, false>);
-        case 4: return crc ? (swap ? k_decode_duo<true, 4, true> : k_decode_duo<true, 4, false>)
-                           : (swap ? k_decode_duo<false, 4, true> : k_decode_duo<false, 4, false>);
-        case 8: return crc ? (swap ? k_decode_duo<true, 8, true> : k_decode_duo<true, 8, false>)
-                           : (swap ? k_decode_duo<false, 8, true> : k_decode_duo<false, 8, false>);
-        default: return nullptr;
-    }
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        return crc ? k_decode_duo<true, T::item, T::swap> : k_decode_duo<false, T::item, T::swap>;
+    });
 }
 
 KernelFn select_rows_kernel(bool crc, int item, bool swap, int k) {
 #if ZHIP_TUNING
     if (k == 4) {  // 16 KiB units (tuning arm)
-        if (crc && item == 4 && !swap) return k_decode_rows<true, 4, false, 4>;
-        return nullptr;
+        return headline_item(crc, item, swap) ? k_decode_rows<true, 4, false, 4> : nullptr;
     }
 #endif
     if (k != 8) return nullptr;
-    switch (item) {
-        case 1: return crc ? k_decode_rows<true, 1, false> : k_decode_rows<false, 1, false>;
-        case 2: return crc ? (swap ? k_decode_rows<true, 2, true> : k_decode_rows<true, 2, false>)
-                           : (swap ? k_decode_rows<false, 2, true> : k_decode_rows<false, 2, false>);
-        case 4: return crc ? (swap ? k_decode_rows<true, 4, true> : k_decode_rows<true, 4, false>)
-                           : (swap ? k_decode_rows<false, 4, true> : k_decode_rows<false, 4, false>);
-        case 8: return crc ? (swap ? k_decode_rows<true, 8, true> : k_decode_rows<true, 8, false>)
-                           : (swap ? k_decode_rows<false, 8, true> : k_decode_rows<false, 8, false>);
-        default: return nullptr;
-    }
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        return crc ? k_decode_rows<true, T::item, T::swap> : k_decode_rows<false, T::item, T::swap>;
+    });
 }
 
 }  // namespace zhip

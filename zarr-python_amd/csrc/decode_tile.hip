@@ -22,6 +22,7 @@
 #include "../../include/zarrhip.h"
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
+#include "zhip_dispatch.h"
 #include "zhip_device.h"
 #include "zhip_decode_common.h"
 
@@ -1605,194 +1606,118 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     }
 }
 
-using KernelFn = void (*)(const DecodeParams);
-using EncodeFn = void (*)(const EncodeParams);
-
-EncodeFn select_encode_tileg_kernel(bool crc, int item, bool swap, int nt) {
+EncodeFn select_encode_tileg_kernel(bool crc, int item, bool swap, EncTilegForm form) {
 #if ZHIP_TUNING
-    if (nt == 6 || nt == 7 || nt == 8 || nt == 9) {  // arms 47 / 50: four / two tiles, arrival words on
-        // lines of their own; arm 63 (8): four tiles, the look-back finalizer; arm 68 (9): four
-        // accumulators through one byte-table operator
+    if (form == kEtgFourSpread || form == kEtgTwoSpread || form == kEtgLookBack || form == kEtgA4) {
+        // arms 47 / 50: four / two tiles, arrival words on lines of their own; arm 63: four tiles,
+        // the look-back finalizer; arm 68: four accumulators through one byte-table operator
         if (!crc) return nullptr;
-#define ZHIP_ETG(I, W)                                                                                      \
-    (nt == 6 ? k_encode_tileg<true, I, W, 4, true> : nt == 8 ? k_encode_tileg<true, I, W, 4, true, true>    \
-     : nt == 9 ? k_encode_tileg<true, I, W, 4, false, false, true> : k_encode_tileg<true, I, W, 2, true>)
-        switch (item) {
-            case 1: return ZHIP_ETG(1, false);
-            case 2: return swap ? ZHIP_ETG(2, true) : ZHIP_ETG(2, false);
-            case 4: return swap ? ZHIP_ETG(4, true) : ZHIP_ETG(4, false);
-            case 8: return swap ? ZHIP_ETG(8, true) : ZHIP_ETG(8, false);
-            default: return nullptr;
-        }
-#undef ZHIP_ETG
+        return for_item(item, swap, [&](auto t) -> EncodeFn {
+            using T = decltype(t);
+            return form == kEtgFourSpread ? k_encode_tileg<true, T::item, T::swap, 4, true>
+                   : form == kEtgLookBack ? k_encode_tileg<true, T::item, T::swap, 4, true, true>
+                   : form == kEtgA4       ? k_encode_tileg<true, T::item, T::swap, 4, false, false, true>
+                                          : k_encode_tileg<true, T::item, T::swap, 2, true>;
+        });
     }
 #endif
-    if (nt == 2) {  // CRC layouts only
+    if (form == kEtgTwo) {  // CRC layouts only
         if (!crc) return nullptr;
-        switch (item) {
-            case 1: return k_encode_tileg<true, 1, false, 2>;
-            case 2: return swap ? k_encode_tileg<true, 2, true, 2> : k_encode_tileg<true, 2, false, 2>;
-            case 4: return swap ? k_encode_tileg<true, 4, true, 2> : k_encode_tileg<true, 4, false, 2>;
-            case 8: return swap ? k_encode_tileg<true, 8, true, 2> : k_encode_tileg<true, 8, false, 2>;
-            default: return nullptr;
-        }
+        return for_item(item, swap, [](auto t) -> EncodeFn {
+            return k_encode_tileg<true, decltype(t)::item, decltype(t)::swap, 2>;
+        });
     }
-    switch (item) {
-        case 1: return crc ? k_encode_tileg<true, 1, false> : k_encode_tileg<false, 1, false>;
-        case 2: return crc ? (swap ? k_encode_tileg<true, 2, true> : k_encode_tileg<true, 2, false>)
-                           : (swap ? k_encode_tileg<false, 2, true> : k_encode_tileg<false, 2, false>);
-        case 4: return crc ? (swap ? k_encode_tileg<true, 4, true> : k_encode_tileg<true, 4, false>)
-                           : (swap ? k_encode_tileg<false, 4, true> : k_encode_tileg<false, 4, false>);
-        case 8: return crc ? (swap ? k_encode_tileg<true, 8, true> : k_encode_tileg<true, 8, false>)
-                           : (swap ? k_encode_tileg<false, 8, true> : k_encode_tileg<false, 8, false>);
-        default: return nullptr;
-    }
+    return for_item(item, swap, [&](auto t) -> EncodeFn {
+        using T = decltype(t);
+        return crc ? k_encode_tileg<true, T::item, T::swap> : k_encode_tileg<false, T::item, T::swap>;
+    });
 }
 
 EncodeFn select_encode_tile_kernel(bool crc, int item, bool swap) {
-    switch (item) {
-        case 1: return crc ? k_encode_tile<true, 1, false> : k_encode_tile<false, 1, false>;
-        case 2: return crc ? (swap ? k_encode_tile<true, 2, true> : k_encode_tile<true, 2, false>)
-                           : (swap ? k_encode_tile<false, 2, true> : k_encode_tile<false, 2, false>);
-        case 4: return crc ? (swap ? k_encode_tile<true, 4, true> : k_encode_tile<true, 4, false>)
-                           : (swap ? k_encode_tile<false, 4, true> : k_encode_tile<false, 4, false>);
-        case 8: return crc ? (swap ? k_encode_tile<true, 8, true> : k_encode_tile<true, 8, false>)
-                           : (swap ? k_encode_tile<false, 8, true> : k_encode_tile<false, 8, false>);
-        default: return nullptr;
-    }
+    return for_item(item, swap, [&](auto t) -> EncodeFn {
+        using T = decltype(t);
+        return crc ? k_encode_tile<true, T::item, T::swap> : k_encode_tile<false, T::item, T::swap>;
+    });
 }
 
-// nt = 2: the two-tile form (CRC layouts whose plan built its constants)
-EncodeFn select_encode_tile4_kernel(bool crc, int item, bool swap, int nt) {
-    if (nt == 2) {
+// two: the two-tile form (CRC layouts whose plan built its constants)
+EncodeFn select_encode_tile4_kernel(bool crc, int item, bool swap, bool two) {
+    if (two) {
         if (!crc) return nullptr;
-        switch (item) {
-            case 1: return k_encode_tile4<true, 1, false, 2>;
-            case 2: return swap ? k_encode_tile4<true, 2, true, 2> : k_encode_tile4<true, 2, false, 2>;
-            case 4: return swap ? k_encode_tile4<true, 4, true, 2> : k_encode_tile4<true, 4, false, 2>;
-            case 8: return swap ? k_encode_tile4<true, 8, true, 2> : k_encode_tile4<true, 8, false, 2>;
-            default: return nullptr;
-        }
+        return for_item(item, swap, [](auto t) -> EncodeFn {
+            return k_encode_tile4<true, decltype(t)::item, decltype(t)::swap, 2>;
+        });
     }
-    switch (item) {
-        case 1: return crc ? k_encode_tile4<true, 1, false> : k_encode_tile4<false, 1, false>;
-        case 2: return crc ? (swap ? k_encode_tile4<true, 2, true> : k_encode_tile4<true, 2, false>)
-                           : (swap ? k_encode_tile4<false, 2, true> : k_encode_tile4<false, 2, false>);
-        case 4: return crc ? (swap ? k_encode_tile4<true, 4, true> : k_encode_tile4<true, 4, false>)
-                           : (swap ? k_encode_tile4<false, 4, true> : k_encode_tile4<false, 4, false>);
-        case 8: return crc ? (swap ? k_encode_tile4<true, 8, true> : k_encode_tile4<true, 8, false>)
-                           : (swap ? k_encode_tile4<false, 8, true> : k_encode_tile4<false, 8, false>);
-        default: return nullptr;
-    }
+    return for_item(item, swap, [&](auto t) -> EncodeFn {
+        using T = decltype(t);
+        return crc ? k_encode_tile4<true, T::item, T::swap> : k_encode_tile4<false, T::item, T::swap>;
+    });
 }
 
 // defer: ZHIP_DF_DEFER (deferred CRC verdicts, PUB 2); otherwise the returning
 // publication (PUB 0), whose launch reports a mismatch itself
 KernelFn select_tileg_kernel(bool crc, int item, bool swap, bool defer) {
-    if (!crc) {
-        switch (item) {
-            case 1: return k_decode_tileg<false, 1, false>;
-            case 2: return swap ? k_decode_tileg<false, 2, true> : k_decode_tileg<false, 2, false>;
-            case 4: return swap ? k_decode_tileg<false, 4, true> : k_decode_tileg<false, 4, false>;
-            case 8: return swap ? k_decode_tileg<false, 8, true> : k_decode_tileg<false, 8, false>;
-            default: return nullptr;
-        }
-    }
-#define ZHIP_TILEG(I, W) (defer ? k_decode_tileg<true, I, W, 2> : k_decode_tileg<true, I, W, 0>)
-    switch (item) {
-        case 1: return ZHIP_TILEG(1, false);
-        case 2: return swap ? ZHIP_TILEG(2, true) : ZHIP_TILEG(2, false);
-        case 4: return swap ? ZHIP_TILEG(4, true) : ZHIP_TILEG(4, false);
-        case 8: return swap ? ZHIP_TILEG(8, true) : ZHIP_TILEG(8, false);
-        default: return nullptr;
-    }
-#undef ZHIP_TILEG
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        if (!crc) return k_decode_tileg<false, T::item, T::swap>;
+        return defer ? k_decode_tileg<true, T::item, T::swap, 2> : k_decode_tileg<true, T::item, T::swap, 0>;
+    });
 }
 
-KernelFn select_tilegw_kernel(int item, bool swap, bool defer, int nt) {  // CRC chains only
-// (nt 2: the two-tile form, always the returning publication on spread lines;
-// tuning: 6 the same on packed words, 5 lanes pick the tile)
+// (kTgwTwo: always the returning publication on spread lines; the forms past
+// kTgwFour exist in the tuning build only and select as kTgwFour elsewhere)
+KernelFn select_tilegw_kernel(int item, bool swap, bool defer, TilegwForm form) {  // CRC chains only
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        if (form == kTgwTwo) return k_decode_tilegw<T::item, T::swap, 0, 2, false, true>;
 #if ZHIP_TUNING
-#define ZHIP_TILEGW(I, W)                                                                          \
-    (nt == 2 ? k_decode_tilegw<I, W, 0, 2, false, true>                                             \
-     : nt == 7 ? k_decode_tilegw<I, W, 0, 2, false, true, true>                                     \
-     : nt == 8 ? k_decode_tilegw<I, W, 0, 2, false, true, false, true>                              \
-     : nt == 5 ? (defer ? k_decode_tilegw<I, W, 2, 4, true> : k_decode_tilegw<I, W, 0, 4, true>)   \
-     : nt == 6 ? k_decode_tilegw<I, W, 0, 2>                                                        \
-             : (defer ? k_decode_tilegw<I, W, 2> : k_decode_tilegw<I, W, 0>))
-#else
-#define ZHIP_TILEGW(I, W)                                                                          \
-    (nt == 2 ? k_decode_tilegw<I, W, 0, 2, false, true>                                             \
-             : (defer ? k_decode_tilegw<I, W, 2> : k_decode_tilegw<I, W, 0>))
+        if (form == kTgwLookBack) return k_decode_tilegw<T::item, T::swap, 0, 2, false, true, true>;
+        if (form == kTgwByteTab) return k_decode_tilegw<T::item, T::swap, 0, 2, false, true, false, true>;
+        if (form == kTgwLanes)
+            return defer ? k_decode_tilegw<T::item, T::swap, 2, 4, true> : k_decode_tilegw<T::item, T::swap, 0, 4, true>;
+        if (form == kTgwPacked) return k_decode_tilegw<T::item, T::swap, 0, 2>;
 #endif
-    switch (item) {
-        case 1: return ZHIP_TILEGW(1, false);
-        case 2: return swap ? ZHIP_TILEGW(2, true) : ZHIP_TILEGW(2, false);
-        case 4: return swap ? ZHIP_TILEGW(4, true) : ZHIP_TILEGW(4, false);
-        case 8: return swap ? ZHIP_TILEGW(8, true) : ZHIP_TILEGW(8, false);
-        default: return nullptr;
-    }
-#undef ZHIP_TILEGW
+        return defer ? k_decode_tilegw<T::item, T::swap, 2> : k_decode_tilegw<T::item, T::swap, 0>;
+    });
 }
 
 KernelFn select_tile4w_kernel(int item, bool swap) {  // CRC chains only
-    switch (item) {
-        case 1: return k_decode_tile4w<1, false>;
-        case 2: return swap ? k_decode_tile4w<2, true> : k_decode_tile4w<2, false>;
-        case 4: return swap ? k_decode_tile4w<4, true> : k_decode_tile4w<4, false>;
-        case 8: return swap ? k_decode_tile4w<8, true> : k_decode_tile4w<8, false>;
-        default: return nullptr;
-    }
+    return for_item(item, swap, [](auto t) -> KernelFn { return k_decode_tile4w<decltype(t)::item, decltype(t)::swap>; });
 }
 
 // two tiles per workgroup (production where the plan built its constants);
-// the tuning build adds one tile per workgroup (arm 37)
-KernelFn select_tile2w_kernel(int item, bool swap, int nt) {  // CRC chains only
+// the tuning build adds one tile per workgroup (arm 37), the split
+// publication (arm 49) and the byte-table chains (arm 67)
+KernelFn select_tile2w_kernel(int item, bool swap, Tile2wForm form) {  // CRC chains only
+    if (!ZHIP_TUNING && form != kT2wTwo) return nullptr;
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
 #if ZHIP_TUNING
-#define ZHIP_T2W(I, W)                                                                                  \
-    (nt == 1 ? k_decode_tile4w<I, W, 1> : nt == 3 ? k_decode_tile4w<I, W, 2, true>                       \
-     : nt == 4 ? k_decode_tile4w<I, W, 2, false, true> : k_decode_tile4w<I, W, 2>)
-#else
-    if (nt != 2) return nullptr;
-#define ZHIP_T2W(I, W) k_decode_tile4w<I, W, 2>
+        if (form == kT2wOne) return k_decode_tile4w<T::item, T::swap, 1>;
+        if (form == kT2wSplit) return k_decode_tile4w<T::item, T::swap, 2, true>;
+        if (form == kT2wByteTab) return k_decode_tile4w<T::item, T::swap, 2, false, true>;
 #endif
-    switch (item) {
-        case 1: return ZHIP_T2W(1, false);
-        case 2: return swap ? ZHIP_T2W(2, true) : ZHIP_T2W(2, false);
-        case 4: return swap ? ZHIP_T2W(4, true) : ZHIP_T2W(4, false);
-        case 8: return swap ? ZHIP_T2W(8, true) : ZHIP_T2W(8, false);
-        default: return nullptr;
-    }
-#undef ZHIP_T2W
+        return k_decode_tile4w<T::item, T::swap, 2>;
+    });
 }
 
 #if ZHIP_TUNING
 KernelFn select_tile4f_kernel(int item, bool swap) {  // CRC chains only
-    switch (item) {
-        case 1: return k_decode_tile4f<1, false>;
-        case 2: return swap ? k_decode_tile4f<2, true> : k_decode_tile4f<2, false>;
-        case 4: return swap ? k_decode_tile4f<4, true> : k_decode_tile4f<4, false>;
-        case 8: return swap ? k_decode_tile4f<8, true> : k_decode_tile4f<8, false>;
-        default: return nullptr;
-    }
+    return for_item(item, swap, [](auto t) -> KernelFn { return k_decode_tile4f<decltype(t)::item, decltype(t)::swap>; });
 }
 #endif
 
 KernelFn select_tile4_kernel(bool crc, int item, bool swap) {
 #if ZHIP_TUNING
-    if (g_tune_arm == 1 && crc && item == 4 && !swap) return k_decode_tile4<true, 4, false, 0>;  // words 16 B apart
-    if (g_tune_arm == 2 && crc && item == 4 && !swap) return k_decode_tile4<true, 4, false, 2>;  // deferred arm
-#endif
-    switch (item) {
-        case 1: return crc ? k_decode_tile4<true, 1, false> : k_decode_tile4<false, 1, false>;
-        case 2: return crc ? (swap ? k_decode_tile4<true, 2, true> : k_decode_tile4<true, 2, false>)
-                           : (swap ? k_decode_tile4<false, 2, true> : k_decode_tile4<false, 2, false>);
-        case 4: return crc ? (swap ? k_decode_tile4<true, 4, true> : k_decode_tile4<true, 4, false>)
-                           : (swap ? k_decode_tile4<false, 4, true> : k_decode_tile4<false, 4, false>);
-        case 8: return crc ? (swap ? k_decode_tile4<true, 8, true> : k_decode_tile4<true, 8, false>)
-                           : (swap ? k_decode_tile4<false, 8, true> : k_decode_tile4<false, 8, false>);
-        default: return nullptr;
+    if (headline_item(crc, item, swap)) {
+        if (g_tune_arm == kArmPub16) return k_decode_tile4<true, 4, false, 0>;  // words 16 B apart
+        if (g_tune_arm == kArmDeferred) return k_decode_tile4<true, 4, false, 2>;  // deferred arm
     }
+#endif
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        return crc ? k_decode_tile4<true, T::item, T::swap> : k_decode_tile4<false, T::item, T::swap>;
+    });
 }
 
 }  // namespace zhip

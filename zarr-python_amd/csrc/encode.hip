@@ -26,6 +26,7 @@
 #include "zhip_device.h"
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
+#include "zhip_dispatch.h"
 #include "zhip_decode_common.h"
 
 namespace zhip {
@@ -607,22 +608,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     p.status[c] = st;
 }
 
-using EncodeFn = void (*)(const EncodeParams);
-
 static EncodeFn pick_encode_il(int item, bool swap, bool aff) {
+    return for_item(item, swap, [&](auto t) -> EncodeFn {
+        using T = decltype(t);
 #if ZHIP_TUNING
-#define ZHIP_EIL(I, W) (aff ? k_encode_il<I, W, true> : k_encode_il<I, W>)  // (arm 46)
-#else
-#define ZHIP_EIL(I, W) k_encode_il<I, W>
+        if (aff) return k_encode_il<T::item, T::swap, true>;  // (arm 46)
 #endif
-    switch (item) {
-        case 1: return ZHIP_EIL(1, false);
-        case 2: return swap ? ZHIP_EIL(2, true) : ZHIP_EIL(2, false);
-        case 4: return swap ? ZHIP_EIL(4, true) : ZHIP_EIL(4, false);
-        case 8: return swap ? ZHIP_EIL(8, true) : ZHIP_EIL(8, false);
-        default: return nullptr;
-    }
-#undef ZHIP_EIL
+        return k_encode_il<T::item, T::swap>;
+    });
 }
 
 // k_encode_quad: k_encode_pair for chunks of at most 16 KiB (one unit per
@@ -728,158 +721,142 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 }
 
 
-template <bool CRC, int ITEM>
-static EncodeFn pick_encode_quad_item(bool swap) {
-    if constexpr (ITEM == 1) return k_encode_quad<CRC, 1, false>;
-    else return swap ? k_encode_quad<CRC, ITEM, true> : k_encode_quad<CRC, ITEM, false>;
-}
-
 static EncodeFn pick_encode_quad(bool crc, int item, bool swap) {
-    switch (item) {
-        case 1: return crc ? pick_encode_quad_item<true, 1>(swap) : pick_encode_quad_item<false, 1>(swap);
-        case 2: return crc ? pick_encode_quad_item<true, 2>(swap) : pick_encode_quad_item<false, 2>(swap);
-        case 4: return crc ? pick_encode_quad_item<true, 4>(swap) : pick_encode_quad_item<false, 4>(swap);
-        case 8: return crc ? pick_encode_quad_item<true, 8>(swap) : pick_encode_quad_item<false, 8>(swap);
-        default: return nullptr;
-    }
+    return for_item(item, swap, [&](auto t) -> EncodeFn {
+        using T = decltype(t);
+        return crc ? k_encode_quad<true, T::item, T::swap> : k_encode_quad<false, T::item, T::swap>;
+    });
 }
 
 template <bool CRC, bool FAST>
 static EncodeFn pick_encode(int item, bool swap) {
-    switch (item) {
-        case 1: return k_encode<CRC, FAST, 1, false>;
-        case 2: return swap ? k_encode<CRC, FAST, 2, true> : k_encode<CRC, FAST, 2, false>;
-        case 4: return swap ? k_encode<CRC, FAST, 4, true> : k_encode<CRC, FAST, 4, false>;
-        case 8: return swap ? k_encode<CRC, FAST, 8, true> : k_encode<CRC, FAST, 8, false>;
-        default: return nullptr;
-    }
+    return for_item(item, swap, [](auto t) -> EncodeFn {
+        return k_encode<CRC, FAST, decltype(t)::item, decltype(t)::swap>;
+    });
 }
 
 static EncodeFn pick_encode_pair(bool crc, int item, bool swap) {
 #if ZHIP_TUNING
-    if (g_tune_arm == 1 && crc && item == 4 && !swap) return k_encode_pair<true, 4, false, true>;  // 11/11/10 tables
+    // (11/11/10 tables)
+    if (g_tune_arm == kArmPub16 && headline_item(crc, item, swap)) return k_encode_pair<true, 4, false, true>;
 #endif
-    switch (item) {
-        case 1: return crc ? k_encode_pair<true, 1, false> : k_encode_pair<false, 1, false>;
-        case 2: return crc ? (swap ? k_encode_pair<true, 2, true> : k_encode_pair<true, 2, false>)
-                           : (swap ? k_encode_pair<false, 2, true> : k_encode_pair<false, 2, false>);
-        case 4: return crc ? (swap ? k_encode_pair<true, 4, true> : k_encode_pair<true, 4, false>)
-                           : (swap ? k_encode_pair<false, 4, true> : k_encode_pair<false, 4, false>);
-        case 8: return crc ? (swap ? k_encode_pair<true, 8, true> : k_encode_pair<true, 8, false>)
-                           : (swap ? k_encode_pair<false, 8, true> : k_encode_pair<false, 8, false>);
-        default: return nullptr;
-    }
+    return for_item(item, swap, [&](auto t) -> EncodeFn {
+        using T = decltype(t);
+        return crc ? k_encode_pair<true, T::item, T::swap> : k_encode_pair<false, T::item, T::swap>;
+    });
 }
 
-EncodeFn select_encode_tile4_kernel(bool crc, int item, bool swap, int nt);  // decode_tile.hip
-EncodeFn select_encode_tile_kernel(bool crc, int item, bool swap);   // decode_tile.hip
-EncodeFn select_encode_tileg_kernel(bool crc, int item, bool swap, int nt);  // decode_tile.hip
+// One launch_encode call: the parameters, where and how wide to launch, and
+// the layout's item type.
+struct EncLaunch {
+    const EncodeParams& p;
+    hipStream_t stream;
+    int max_grid;  // CUs * 8
+    bool crc, swap;
+    int item;
+};
 
-int launch_encode(const EncodeParams& p, hipStream_t stream, int max_grid) {
-    const bool crc = (p.lflags & ZHIP_LF_CRC) != 0;
-    const bool swap = (p.lflags & ZHIP_LF_SWAP) != 0;
-    if (p.tile4) {  // transposed layouts with full tiles (k_encode_tile4)
-        // two tiles per workgroup where the plan built their constants (tuning
-        // arm 38 keeps four)
-        const int nt = (crc && p.kq2 && g_tune_arm != 38) ? 2 : 4;
-        EncodeFn fn = select_encode_tile4_kernel(crc, p.g.itemsize, swap, nt);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_chunks == 0) return ZHIP_OK;
-        EncodeParams q = p;
-        if (nt == 2) q.kq4 = p.kq2;
-        g_last_kernel = nt == 2 ? "k_encode_tile2" : "k_encode_tile4";
-        hipLaunchKernelGGL(fn, dim3(p.n_chunks * (p.t_per_chunk / (uint32_t)nt)), dim3(kThreads), 0, stream, q);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    if (p.tile == 2) {  // full selections, tiles grouped by four at a uniform step (k_encode_tileg)
-        // (tuning arm 36: two workgroups per group, two tiles each -- C3 in 128^3
-        // chunks 33.1-34.1 vs 32.8-33.6 us graph-timed, no gain, profiles/r05/p/)
-        const int nt = (crc && (g_tune_arm == 36 || g_tune_arm == 50)) ? 2 : 4;
-        // (tuning arms 47 / 50: four / two tiles, arrival words on lines of their own)
-        const bool spr = ZHIP_TUNING && crc && (g_tune_arm == 47 || g_tune_arm == 50);
-        // (tuning arm 63: four tiles, the look-back finalizer, while fewer chunks than CUs)
-        const bool lb = ZHIP_TUNING && crc && g_tune_arm == 63 && p.n_chunks < (uint32_t)(max_grid / 8) &&
-                        (p.n_groups <= 16u || p.n_sub);
-        // (tuning arm 68: four accumulators through one byte-table operator)
-        const bool a4c = ZHIP_TUNING && crc && g_tune_arm == 68 && p.g_a4 != nullptr;
-        EncodeFn fn = select_encode_tileg_kernel(crc, p.g.itemsize, swap,
-                                                 a4c ? 9 : lb ? 8 : spr ? (nt == 4 ? 6 : 7) : nt);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_chunks == 0) return ZHIP_OK;
-        const uint64_t grid = (uint64_t)p.n_chunks * p.n_groups * (uint32_t)(4 / nt);
-        if (grid >= (1ull << 31) || p.n_groups >= 65536u) return ZHIP_E_UNSUPPORTED;
-        // (the last arrival of each chunk writes its non-empty flag)
-        g_last_kernel = nt == 2 ? (spr ? "k_encode_tileg2s" : "k_encode_tileg2") : spr ? "k_encode_tilegs" : "k_encode_tileg";
-        if (lb) g_last_kernel = "k_encode_tileg_lb";
-        if (a4c) g_last_kernel = "k_encode_tileg_a4";
-        hipLaunchKernelGGL(fn, dim3((uint32_t)grid), dim3(kThreads), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    if (p.tile) {  // other transposed layouts / prefix selections (k_encode_tile)
-        EncodeFn fn = select_encode_tile_kernel(crc, p.g.itemsize, swap);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_chunks == 0) return ZHIP_OK;
-        const uint64_t gpc = (p.t_per_chunk + 3u) / 4u;  // four tiles per workgroup
-        if ((uint64_t)p.n_chunks * gpc >= (1ull << 31) || gpc >= 65536u) return ZHIP_E_UNSUPPORTED;
-        // (the last arrival of each chunk writes its non-empty flag)
-        g_last_kernel = "k_encode_tile";
-        hipLaunchKernelGGL(fn, dim3((uint32_t)(p.n_chunks * gpc)), dim3(kThreads), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    if (p.rowmap && p.seg == (uint32_t)kWgStride * kDefaultBlocks && !(p.tune & kTunePersist) && p.nseg == 1u &&
-        p.E <= 4u * kWgStride && g_tune_arm != 11) {  // chunks of <= 16 KiB: four per workgroup (arm 11: pairs)
-        EncodeFn fn = pick_encode_quad(crc, p.g.itemsize, swap);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_units == 0) return ZHIP_OK;
-        g_last_kernel = "k_encode_quad";
-        hipLaunchKernelGGL(fn, dim3((p.n_units + 3u) / 4u), dim3(kThreads), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    if (p.rowmap && p.seg == (uint32_t)kWgStride * kDefaultBlocks && !(p.tune & kTunePersist) && crc &&
-        p.il_S >= 8u && p.nseg <= 32u && g_tune_arm != 34) {
+// transposed layouts with full tiles (k_encode_tile4)
+static int launch_encode_tile4(const EncLaunch& L) {
+    const EncodeParams& p = L.p;
+    // two tiles per workgroup where the plan built their constants (tuning
+    // arm 38 keeps four)
+    const bool two = L.crc && p.kq2 && g_tune_arm != kArmTileFour;
+    EncodeParams q = p;
+    if (two) q.kq4 = p.kq2;
+    return fire(select_encode_tile4_kernel(L.crc, L.item, L.swap, two), two ? "k_encode_tile2" : "k_encode_tile4",
+                p.n_chunks * (p.t_per_chunk / (two ? 2u : 4u)), kThreads, q, L.stream);
+}
+
+// full selections, tiles grouped by four at a uniform step (k_encode_tileg)
+static int launch_encode_tileg(const EncLaunch& L) {
+    const EncodeParams& p = L.p;
+    const bool crc = L.crc;
+    // (tuning arm 36: two workgroups per group, two tiles each -- C3 in 128^3
+    // chunks 33.1-34.1 vs 32.8-33.6 us graph-timed, no gain, profiles/r05/p/)
+    const bool two = crc && (g_tune_arm == kArmEncTileg2 || g_tune_arm == kArmEncTileg2Spread);
+    // (tuning arms 47 / 50: four / two tiles, arrival words on lines of their own)
+    const bool spr = ZHIP_TUNING && crc && (g_tune_arm == kArmEncTilegSpread || g_tune_arm == kArmEncTileg2Spread);
+    // (tuning arm 63: four tiles, the look-back finalizer, while fewer chunks than CUs)
+    const bool lb = ZHIP_TUNING && crc && g_tune_arm == kArmEncTilegLookBack &&
+                    p.n_chunks < (uint32_t)(L.max_grid / 8) && (p.n_groups <= 16u || p.n_sub);
+    // (tuning arm 68: four accumulators through one byte-table operator)
+    const bool a4c = ZHIP_TUNING && crc && g_tune_arm == kArmEncTilegA4 && p.g_a4 != nullptr;
+    EncodeFn fn = select_encode_tileg_kernel(crc, L.item, L.swap,
+                                             a4c ? kEtgA4 : lb ? kEtgLookBack
+                                             : spr ? (two ? kEtgTwoSpread : kEtgFourSpread) : two ? kEtgTwo : kEtgFour);
+    const uint64_t grid = (uint64_t)p.n_chunks * p.n_groups * (two ? 2u : 1u);
+    // (an empty batch returns before the range checks)
+    if (p.n_chunks != 0 && (grid >= (1ull << 31) || p.n_groups >= 65536u)) return ZHIP_E_UNSUPPORTED;
+    // (the last arrival of each chunk writes its non-empty flag)
+    return fire(fn, a4c ? "k_encode_tileg_a4" : lb ? "k_encode_tileg_lb"
+                    : two ? (spr ? "k_encode_tileg2s" : "k_encode_tileg2") : spr ? "k_encode_tilegs" : "k_encode_tileg",
+                (uint32_t)grid, kThreads, p, L.stream);
+}
+
+// other transposed layouts / prefix selections (k_encode_tile)
+static int launch_encode_tile(const EncLaunch& L) {
+    const EncodeParams& p = L.p;
+    const uint64_t gpc = (p.t_per_chunk + 3u) / 4u;  // four tiles per workgroup
+    // (an empty batch returns before the range checks)
+    if (p.n_chunks != 0 && ((uint64_t)p.n_chunks * gpc >= (1ull << 31) || gpc >= 65536u))
+        return ZHIP_E_UNSUPPORTED;
+    // (the last arrival of each chunk writes its non-empty flag)
+    return fire(select_encode_tile_kernel(L.crc, L.item, L.swap), "k_encode_tile", (uint32_t)(p.n_chunks * gpc), kThreads, p,
+                L.stream);
+}
+
+// Row-mapped layouts in 32 KiB units: quad, il, pair
+static int launch_encode_rows(const EncLaunch& L) {
+    const EncodeParams& p = L.p;
+    if (p.nseg == 1u && p.E <= 4u * kWgStride && g_tune_arm != kArmNoLead4)
+        // chunks of <= 16 KiB: four per workgroup (arm 11: pairs)
+        return fire(pick_encode_quad(L.crc, L.item, L.swap), "k_encode_quad", (p.n_units + 3u) / 4u, kThreads, p, L.stream);
+    if (L.crc && p.il_S >= 8u && p.nseg <= 32u && g_tune_arm != kArmEncNoIl)
         // one unit per workgroup, steps interleaved in groups of eight (k_encode_il;
         // tuning arm 34 keeps k_encode_pair)
-        EncodeFn fn = pick_encode_il(p.g.itemsize, swap, p.aff_ok != 0);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_units == 0) return ZHIP_OK;
-        g_last_kernel = "k_encode_il";
-        hipLaunchKernelGGL(fn, dim3(p.n_units), dim3(kThreads), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
+        return fire(pick_encode_il(L.item, L.swap, p.aff_ok != 0), "k_encode_il", p.n_units, kThreads, p, L.stream);
+    g_last_kernel = "k_encode_pair";  // (named before its checks)
+    EncodeFn fn = pick_encode_pair(L.crc, L.item, L.swap);
+    if (!fn) return ZHIP_E_UNSUPPORTED;
+    if (p.n_units == 0) return ZHIP_OK;
+    // an even unit count <= 32 per chunk: the last arrival of each chunk writes
+    // its non-empty flag; otherwise the kernel ORs into the flags -> zero them
+    if ((p.nseg & 1u) || p.nseg > 32u) {
+        if (hipMemsetAsync(p.nonempty, 0, (size_t)p.n_chunks * sizeof(uint32_t), L.stream) != hipSuccess)
+            return ZHIP_E_HIP;
     }
-    if (p.rowmap && p.seg == (uint32_t)kWgStride * kDefaultBlocks && !(p.tune & kTunePersist)) {
-        g_last_kernel = "k_encode_pair";
-        EncodeFn fn = pick_encode_pair(crc, p.g.itemsize, swap);
-        if (!fn) return ZHIP_E_UNSUPPORTED;
-        if (p.n_units == 0) return ZHIP_OK;
-        // an even unit count <= 32 per chunk: the last arrival of each chunk writes
-        // its non-empty flag; otherwise the kernel ORs into the flags -> zero them
-        if ((p.nseg & 1u) || p.nseg > 32u) {
-            if (hipMemsetAsync(p.nonempty, 0, (size_t)p.n_chunks * sizeof(uint32_t), stream) != hipSuccess)
-                return ZHIP_E_HIP;
-        }
-        const uint32_t grid = (p.n_units + 1u) / 2u;
-        EncodeParams q = p;
-        q.xcd_run = (!(p.tune & kTuneNoXcd) && grid % 8u == 0u && grid <= (uint32_t)(max_grid / 8) * 4u) ? grid / 8u
-                                                                                                      : 0u;
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), 0, stream, q);
-        return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
-    }
-    EncodeFn fn = crc ? (p.fast ? pick_encode<true, true>(p.g.itemsize, swap) : pick_encode<true, false>(p.g.itemsize, swap))
-                      : (p.fast ? pick_encode<false, true>(p.g.itemsize, swap) : pick_encode<false, false>(p.g.itemsize, swap));
+    const uint32_t grid = (p.n_units + 1u) / 2u;
+    EncodeParams q = p;
+    q.xcd_run = (!(p.tune & kTuneNoXcd) && grid % 8u == 0u && grid <= (uint32_t)(L.max_grid / 8) * 4u) ? grid / 8u : 0u;
+    return fire(fn, "k_encode_pair", grid, kThreads, q, L.stream);
+}
+
+// the persistent k_encode: a resident grid of workgroups over the units
+static int launch_encode_persistent(const EncLaunch& L) {
+    const EncodeParams& p = L.p;
+    EncodeFn fn = L.crc ? (p.fast ? pick_encode<true, true>(L.item, L.swap) : pick_encode<true, false>(L.item, L.swap))
+                        : (p.fast ? pick_encode<false, true>(L.item, L.swap) : pick_encode<false, false>(L.item, L.swap));
     if (!fn) return ZHIP_E_UNSUPPORTED;
     if (p.n_units == 0) return ZHIP_OK;
     // the persistent encode ORs each unit's non-empty bit into its chunk's flag
-    if (hipMemsetAsync(p.nonempty, 0, (size_t)p.n_chunks * sizeof(uint32_t), stream) != hipSuccess)
+    if (hipMemsetAsync(p.nonempty, 0, (size_t)p.n_chunks * sizeof(uint32_t), L.stream) != hipSuccess)
         return ZHIP_E_HIP;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), kThreads, 0) ==
-            hipSuccess && per_cu > 0)
-        max_grid = (max_grid / 8) * per_cu;
-    if (g_tune_max_grid > 0) max_grid = g_tune_max_grid;
-    const uint32_t grid = p.n_units < (uint32_t)max_grid ? p.n_units : (uint32_t)max_grid;
-    g_last_kernel = "k_encode";
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;
+    const uint32_t resident = (uint32_t)resident_grid(fn, L.max_grid);
+    return fire(fn, "k_encode", p.n_units < resident ? p.n_units : resident, kThreads, p, L.stream);
+}
+
+// The kernel of an encode, by layout: the tile kernels of transposed layouts
+// (tile4, grouped tiles, tile), the row-mapped kernels, else the generic
+// persistent k_encode.
+int launch_encode(const EncodeParams& p, hipStream_t stream, int max_grid) {
+    const EncLaunch L = {p, stream, max_grid, (p.lflags & ZHIP_LF_CRC) != 0, (p.lflags & ZHIP_LF_SWAP) != 0, p.g.itemsize};
+    if (p.tile4) return launch_encode_tile4(L);
+    if (p.tile == 2) return launch_encode_tileg(L);
+    if (p.tile) return launch_encode_tile(L);
+    if (p.rowmap && p.seg == (uint32_t)kWgStride * kDefaultBlocks && !(p.tune & kTunePersist))
+        return launch_encode_rows(L);
+    return launch_encode_persistent(L);
 }
 
 // ---------------------------------------------------------------------------

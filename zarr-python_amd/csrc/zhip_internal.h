@@ -285,6 +285,76 @@ constexpr uint32_t g_tune_bits = 0;
 constexpr int g_tune_arm = 0;
 #endif
 
+// The values of ZHIP_TUNE_ARM (g_tune_arm): the list of record.  The numbers
+// are frozen (tests, scripts/ and profiles/ carry them).  An arm changes only
+// the launches of the kernel family named with it; everywhere else, and for
+// any number not listed, the production rule holds.  Most arm kernels exist
+// for the headline item type only (4-byte little-endian items, CRC).
+enum Arm : int {
+    kArmProduction = 0,
+    kArmPub16 = 1,          // k_decode_il / k_decode_tile4: publication words 16 B apart (round 3);
+                            // k_encode_pair: 11/11/10 tables
+    kArmDeferred = 2,       // k_decode_il / k_decode_tile4: deferred verdicts; tile layouts: k_decode_tile4 /
+                            // k_decode_tileg / four-tile k_decode_tilegw, the returning publication
+    kArmNoWaveTile = 5,     // tile layouts: k_decode_tile4 / k_decode_tileg where the wave-per-tile kernels would run
+    kArmEncPub16 = 9,       // encodes: chunks' publication words 16 B apart, not a line
+    kArmNoLead4 = 11,       // chunks of <= 16 KiB: the pair kernels, not k_decode_lead4 / k_encode_quad
+    kArmLead4 = 12,         // chunks of <= 8 KiB: four per workgroup (k_decode_lead4)
+    kArmLead8 = 13,         // chunks of <= 8 KiB: eight per workgroup (k_decode_lead8)
+    kArmIlq2 = 20,          // k_decode_ilq: two units per workgroup
+    kArmIlq4 = 21,          // k_decode_ilq: four
+    kArmIlq1Glds = 22,      // k_decode_ilq: one, tables by LDS-DMA
+    kArmIlq2Glds = 23,      // k_decode_ilq: two, tables by LDS-DMA
+    kArmIlq4Glds = 24,      // k_decode_ilq: four, tables by LDS-DMA
+    kArmIlc = 25,           // k_decode_ilc: tables built in LDS, predicted loads first
+    kArmIlw1024 = 26,       // k_decode_ilw: 1024 lanes per unit
+    kArmIlw512 = 27,        // k_decode_ilw: 512 lanes per unit, whatever the grid
+    kArmProbeArgs = 28,     // k_probe: a decode-shaped grid with the decode's arguments (results invalid)
+    kArmProbeLds = 29,      // k_probe: plus k_decode_il's LDS footprint
+    kArmProbeHeader = 30,   // k_probe: plus each workgroup's header chain
+    kArmIlw1024Reg = 31,    // k_decode_ilw: 1024 lanes, the lane multiply in registers
+    kArmIlw512Reg = 32,     // k_decode_ilw: 512 lanes, the lane multiply in registers
+    kArmKeepIl = 33,        // small grids: k_decode_il (read nowhere: any arm the small-grid rule does not name does this)
+    kArmEncNoIl = 34,       // encodes: k_encode_pair where k_encode_il would run
+    kArmIlp = 35,           // k_decode_ilp: index entry off the stores' path (predicted plans)
+    kArmEncTileg2 = 36,     // k_encode_tileg: two workgroups per group, two tiles each
+    kArmTile1w = 37,        // k_decode_tile4w: one tile per workgroup
+    kArmTileFour = 38,      // k_decode_tile4w / k_decode_tilegw / k_encode_tile4: four tiles per workgroup, not two
+    kArmTilePairs = 39,     // layouts that tile4 declines: k_decode_tile4w<2> over consecutive tile pairs (k_decode_tilep)
+    kArmTilegLanes = 40,    // k_decode_tilegw: four tiles, lanes pick the tile
+    kArmIlh = 41,           // k_decode_ilh with the returning publication
+    kArmIlw512Half = 42,    // k_decode_ilw: 512 lanes, half the lane multiply in registers
+    kArmRowMap = 45,        // ZHIP_DF_WHOLE decodes: keep the row-map loads (no AFF form)
+    kArmEncAff = 46,        // k_encode_il: the AFF form for ZHIP_DF_WHOLE encodes
+    kArmEncTilegSpread = 47,   // k_encode_tileg: four tiles, arrival words on lines of their own
+    kArmTilegPacked = 48,   // k_decode_tilegw's two-tile form: the arrival words packed (round-4 layout)
+    kArmSplitPub = 49,      // k_decode_il / k_decode_ilw / k_decode_tile4w: the split publication
+    kArmEncTileg2Spread = 50,  // k_encode_tileg: two tiles, arrival words on lines of their own
+    kArmIlPrioRunEnd = 51,  // k_decode_il (AFF): wave priority at the run end
+    kArmIlPrioLoads = 52,   // k_decode_il (AFF): at the load issue
+    kArmIlPrioBoth = 53,    // k_decode_il (AFF): both
+    kArmIlPrioTables = 54,  // k_decode_il (AFF): to the tables (production)
+    kArmIlPrioTablesEnd = 55,  // k_decode_il (AFF): 54 + run end
+    kArmIlNoPrio = 56,      // k_decode_il (AFF): no priority (round-5 production)
+    kArmIlXcd = 57,         // k_decode_il (AFF): 54 + XCD-contiguous eighths
+    kArmLookBack = 58,      // k_decode_il / k_decode_ilw (AFF): the look-back finalizer
+    kArmIlhLookBack = 59,   // k_decode_ilh: the look-back finalizer without the AFF form
+    kArmIlhProduction = 60, // small grids: production's k_decode_ilh, by number
+    kArmIlw512Small = 61,   // small grids: k_decode_ilw512 (round-5 production), not k_decode_ilh
+    kArmTilegLookBack = 62, // k_decode_tilegw's two-tile form: the look-back finalizer
+    kArmEncTilegLookBack = 63,  // k_encode_tileg: four tiles, the look-back finalizer
+    kArmIlStoreWt = 64,     // k_decode_il (AFF): write-through stores
+    kArmIlStoreNt = 65,     // k_decode_il (AFF): nontemporal buffer stores
+    kArmTilegByteTab = 66,  // k_decode_tilegw's two-tile form: byte-table chains
+    kArmTile2wByteTab = 67, // k_decode_tile4w's two-tile form: byte-table chains
+    kArmEncTilegA4 = 68,    // k_encode_tileg: four accumulators through one byte-table operator
+    kArmIlS16 = 69,         // k_decode_il: interleave stride 16
+    kArmIlS32 = 70,         // k_decode_il: 32
+    kArmIlS8 = 71,          // k_decode_il: 8
+    kArmEncIlS8 = 73,       // k_encode_il: interleave stride 8
+};
+inline bool arm_in(Arm lo, Arm hi) { return g_tune_arm >= lo && g_tune_arm <= hi; }
+
 struct EncodeParams {
     const uint8_t* arr;   // source array base (device)
     uint8_t* dst;         // encoded destination buffer
@@ -367,6 +437,91 @@ int launch_encode(const EncodeParams& p, hipStream_t stream, int max_grid);
 int launch_shard_pack(const PackParams& p, uint32_t n_shards, hipStream_t stream);
 int launch_dv_check(const zhip_dv_ref* d_refs, uint32_t n_refs, hipStream_t stream);
 int debug_stamps(uint64_t* host_out, uint32_t n_wg);
+
+// Kernel selection: (layout flags, item type, form) -> instantiation, nullptr
+// where none exists.  Each selector lives beside its kernels; launch_decode /
+// launch_encode (decode.hip / encode.hip) call them.
+using KernelFn = void (*)(const DecodeParams);
+using EncodeFn = void (*)(const EncodeParams);
+
+// select_pair_kernel: the two-unit kernel, its tuning forms and the kernels
+// of its family (the values past kPairTwo exist in the tuning build only,
+// except the lead kernels)
+enum PairForm {
+    kPairSingle = 1,      // kTuneSingle: one unit per workgroup
+    kPairTwo = 2,         // k_decode_pair
+    kPairNoLookups = 5,   // kTuneSkipCrc: VARIANT 3
+    kPairPrio = 6,        // kTunePrio: VARIANT 6
+    kPairDeferB = 7,      // kTuneDeferB: VARIANT 7
+    kPairPrioDeferB = 8,  // both: VARIANT 8
+    kPairLead = 9,        // k_decode_lead (no data CRC, leading index-check workgroups)
+    kPairLead4 = 10,      // k_decode_lead4: chunks of <= 16 KiB, four per workgroup
+    kPairLead8 = 11,      // k_decode_lead4<.., 8>: chunks of <= 8 KiB, eight per workgroup
+};
+// select_ilw_kernel (all but kIlw512 in the tuning build only)
+enum IlwForm {
+    kIlw512 = 512,          // 512 lanes per unit (production)
+    kIlw1024 = 1024,        // 1024 lanes
+    kIlw512Half = 513,      // 512 lanes, half the lane multiply in registers (kArmIlw512Half)
+    kIlw512Split = 515,     // the split publication (kArmSplitPub; AFF)
+    kIlw512LookBack = 516,  // the look-back finalizer (kArmLookBack; AFF)
+};
+// select_tile2w_kernel (all but kT2wTwo in the tuning build only)
+enum Tile2wForm {
+    kT2wOne = 1,      // one tile per workgroup (kArmTile1w)
+    kT2wTwo = 2,      // two (production)
+    kT2wSplit = 3,    // two, the split publication (kArmSplitPub)
+    kT2wByteTab = 4,  // two, byte-table chains (kArmTile2wByteTab)
+};
+// select_tilegw_kernel (past kTgwFour in the tuning build only)
+enum TilegwForm {
+    kTgwTwo = 2,       // two tiles per workgroup, returning publication on spread lines (production)
+    kTgwFour = 4,      // four tiles
+    kTgwLanes = 5,     // four tiles, lanes pick the tile (kArmTilegLanes)
+    kTgwPacked = 6,    // two tiles, arrival words packed (kArmTilegPacked)
+    kTgwLookBack = 7,  // two tiles, the look-back finalizer (kArmTilegLookBack)
+    kTgwByteTab = 8,   // two tiles, byte-table chains (kArmTilegByteTab)
+};
+// select_encode_tileg_kernel (past kEtgFour in the tuning build only)
+enum EncTilegForm {
+    kEtgTwo = 2,         // two tiles per workgroup (CRC layouts; kArmEncTileg2)
+    kEtgFour = 4,        // four (production)
+    kEtgFourSpread = 6,  // four, arrival words on lines of their own (kArmEncTilegSpread)
+    kEtgTwoSpread = 7,   // two, the same (kArmEncTileg2Spread)
+    kEtgLookBack = 8,    // four, the look-back finalizer (kArmEncTilegLookBack)
+    kEtgA4 = 9,          // four accumulators through one byte-table operator (kArmEncTilegA4)
+};
+
+// decode_rows.hip
+KernelFn select_rows_kernel(bool crc, int item, bool swap, int k);
+KernelFn select_pair_kernel(bool crc, int item, bool swap, PairForm form);
+KernelFn select_duo_kernel(bool crc, int item, bool swap);
+KernelFn select_il_kernel(bool crc, int item, bool swap, bool aff);
+KernelFn select_ilw_kernel(int item, bool swap, IlwForm form, bool lmr, bool aff);
+KernelFn select_ilh_kernel(int item, bool swap, bool lb, bool aff);
+#if ZHIP_TUNING
+KernelFn select_il_kernel_lean(bool crc, int item, bool swap);
+KernelFn select_il_kernel_tuned(bool crc, int item, bool swap);
+KernelFn select_il_kernel_arm(bool crc, int item, bool swap, int arm);
+KernelFn select_il_kernel_cf(bool crc, int item, bool swap);
+KernelFn select_il_kernel_regmul(bool crc, int item, bool swap, bool occ6);
+KernelFn select_xw_kernel(bool crc, int item, bool swap);
+KernelFn select_ilq_kernel(int item, bool swap, int nq, bool glds);
+KernelFn select_ilc_kernel(int item, bool swap);
+KernelFn select_ilp_kernel(int item, bool swap);
+#endif
+// decode_tile.hip
+#if ZHIP_TUNING
+KernelFn select_tile4f_kernel(int item, bool swap);
+#endif
+KernelFn select_tile4_kernel(bool crc, int item, bool swap);
+KernelFn select_tile4w_kernel(int item, bool swap);
+KernelFn select_tile2w_kernel(int item, bool swap, Tile2wForm form);
+KernelFn select_tilegw_kernel(int item, bool swap, bool defer, TilegwForm form);
+KernelFn select_tileg_kernel(bool crc, int item, bool swap, bool defer);
+EncodeFn select_encode_tile4_kernel(bool crc, int item, bool swap, bool two);
+EncodeFn select_encode_tile_kernel(bool crc, int item, bool swap);
+EncodeFn select_encode_tileg_kernel(bool crc, int item, bool swap, EncTilegForm form);
 
 }  // namespace zhip
 
