@@ -407,6 +407,62 @@ int zhip_decode_mapped(const zhip_plan *plan, const void *src, uint64_t src_size
                        zhip_status *d_index_status, uint32_t decode_flags,
                        const zhip_predict *pred, const zhip_rowblk *d_rowmap, void *stream);
 
+/* The arguments of one zhip_decode_mapped call (all but the stream), as a
+ * record: one entry of zhip_decode_mapped_multi's batch. */
+typedef struct zhip_mapped_args {
+    const zhip_plan *plan;
+    const void *src;
+    uint64_t src_size;
+    void *out;
+    const zhip_chunk *d_chunks;
+    uint32_t n_chunks;
+    uint32_t _pad0;
+    const zhip_sel *d_sels;
+    zhip_status *d_status;
+    uint32_t *d_workspace;
+    uint32_t *d_errflag;
+    const zhip_chunk *d_index_chunks;
+    uint32_t n_index;
+    uint32_t _pad1;
+    zhip_status *d_index_status;
+    uint32_t decode_flags;
+    uint32_t _pad2;
+    const zhip_predict *pred;
+    const zhip_rowblk *d_rowmap;
+} zhip_mapped_args;
+
+/* The most entries one zhip_decode_mapped_multi call takes (3). */
+uint32_t zhip_multi_max(void);
+
+/* n INDEPENDENT zhip_decode_mapped calls in ONE kernel launch: entry i's
+ * workgroups follow entry i - 1's in one grid of k_decode_il, so consecutive
+ * decodes share one start-up and one tail and no kernel boundary separates
+ * them.  Results (out bytes, statuses, error words, deferred verdicts) are
+ * those of the n separate calls in any order; the entries must therefore not
+ * depend on one another: the caller guarantees that no entry's out bytes are
+ * another's (nothing is ordered inside the launch), and no two entries may
+ * share a workspace or status table (checked).
+ * ZHIP_E_UNSUPPORTED, with NOTHING launched, unless 2 <= n <= zhip_multi_max(),
+ * every entry alone would launch the interleaved whole-row decode
+ * "k_decode_il" (CRC chains, chunks of a multiple of 8 x 32 KiB, a row map,
+ * more than 512 units), all of them the same instantiation of it (item size,
+ * byte swap, ZHIP_DF_WHOLE form), and the grids together stay below 2^31
+ * workgroups; the caller then issues the entries one by one.  An entry's own
+ * argument errors are reported as zhip_decode_mapped reports them, also
+ * before anything is launched.  Afterwards zhip_last_kernel() is
+ * "k_decode_il": the same kernel body. */
+int zhip_decode_mapped_multi(const zhip_mapped_args *args, uint32_t n, void *stream);
+/* CPU-only test hook: zhip_decode_mapped_multi's checks and return code with
+ * nothing launched; the plans need not be uploaded and no pointer is read.
+ * (A plan that was never uploaded has no tables for the small-launch kernels,
+ * so an entry of at most 512 units is declined only for an uploaded plan.) */
+int zhip_decode_mapped_multi_check(const zhip_mapped_args *args, uint32_t n);
+
+/* Decode and encode kernel launches this process issued so far (zhip_decode*,
+ * zhip_encode*; one per zhip_decode_mapped_multi call): a diagnostic for
+ * tests; not synchronised across threads. */
+uint64_t zhip_launch_count(void);
+
 /* Process-wide tuning / ablation knobs for measurement (never needed for
  * correct operation): ZHIP_TUNE_MAX_GRID = persistent-grid cap (0 = auto),
  * ZHIP_TUNE_ABLATION = ablation bits (0 = production). */

@@ -1050,15 +1050,24 @@ int zhip_rows_map(const zhip_plan* plan, const zhip_sel* h_sels, uint32_t n_sels
     return ZHIP_OK;
 }
 
-int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size, void* out,
-                       const zhip_chunk* d_chunks, uint32_t n_chunks, const zhip_sel* d_sels,
-                       zhip_status* d_status, uint32_t* d_workspace, uint32_t* d_errflag,
-                       const zhip_chunk* d_index_chunks, uint32_t n_index, zhip_status* d_index_status,
-                       uint32_t decode_flags, const zhip_predict* pred, const zhip_rowblk* d_rowmap,
-                       void* stream) {
+// The argument checks and kernel parameters of one zhip_decode_mapped call
+// (zhip_decode_mapped launches them, zhip_decode_mapped_multi several in one
+// grid).  `empty`: nothing to decode, p is not filled.
+extern "C++" {
+static int mapped_params(const zhip_plan* plan, const void* src, uint64_t src_size, void* out,
+                         const zhip_chunk* d_chunks, uint32_t n_chunks, const zhip_sel* d_sels,
+                         zhip_status* d_status, uint32_t* d_workspace, uint32_t* d_errflag,
+                         const zhip_chunk* d_index_chunks, uint32_t n_index, zhip_status* d_index_status,
+                         uint32_t decode_flags, const zhip_predict* pred, const zhip_rowblk* d_rowmap,
+                         DecodeParams& p, bool& empty, bool dry = false) {
+    // (dry: zhip_decode_mapped_multi_check -- nothing is launched, so the plan's tables may be absent)
+    empty = false;
     if (!plan) return set_err(ZHIP_E_INVALID, "null plan");
-    if (!plan->d_tables) return set_err(ZHIP_E_INVALID, "plan not uploaded (zhip_plan_upload)");
-    if (n_chunks == 0 && n_index == 0) return ZHIP_OK;
+    if (!plan->d_tables && !dry) return set_err(ZHIP_E_INVALID, "plan not uploaded (zhip_plan_upload)");
+    if (n_chunks == 0 && n_index == 0) {
+        empty = true;
+        return ZHIP_OK;
+    }
     if (!src || !d_chunks || !d_sels || !d_status || !d_workspace || !d_errflag)
         return set_err(ZHIP_E_INVALID, "null device pointer");
     if (n_index) {
@@ -1075,7 +1084,7 @@ int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size
     if (!(L.flags & ZHIP_LF_NO_WRITE) && !out) return set_err(ZHIP_E_INVALID, "null out");
     const uint64_t units = (uint64_t)n_chunks * plan->nseg;
     if (units >= (1ull << 32)) return set_err(ZHIP_E_UNSUPPORTED, "too many units in one batch");
-    DecodeParams p{};
+    p = DecodeParams{};
     p.src = static_cast<const uint8_t*>(src);
     p.src_size = src_size;
     p.out = static_cast<uint8_t*>(out);
@@ -1270,10 +1279,64 @@ int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size
     }
     if (p.rows && units >= (1ull << 31)) return set_err(ZHIP_E_UNSUPPORTED, "too many units for a row decode");
     fill_pair_hot(p);
-    int rc = launch_decode(p, static_cast<hipStream_t>(stream), plan->max_grid);
+    return ZHIP_OK;
+}
+}
+
+int zhip_decode_mapped(const zhip_plan* plan, const void* src, uint64_t src_size, void* out,
+                       const zhip_chunk* d_chunks, uint32_t n_chunks, const zhip_sel* d_sels,
+                       zhip_status* d_status, uint32_t* d_workspace, uint32_t* d_errflag,
+                       const zhip_chunk* d_index_chunks, uint32_t n_index, zhip_status* d_index_status,
+                       uint32_t decode_flags, const zhip_predict* pred, const zhip_rowblk* d_rowmap,
+                       void* stream) {
+    DecodeParams p;
+    bool empty;
+    int rc = mapped_params(plan, src, src_size, out, d_chunks, n_chunks, d_sels, d_status, d_workspace, d_errflag,
+                           d_index_chunks, n_index, d_index_status, decode_flags, pred, d_rowmap, p, empty);
+    if (rc != ZHIP_OK || empty) return rc;
+    rc = launch_decode(p, static_cast<hipStream_t>(stream), plan->max_grid);
     if (rc == ZHIP_E_UNSUPPORTED) return set_err(rc, "no kernel for this layout");
     if (rc != ZHIP_OK) return set_err(rc, std::string("launch failed: ") + hipGetErrorString(hipGetLastError()));
     return ZHIP_OK;
+}
+
+uint32_t zhip_multi_max(void) { return (uint32_t)ZHIP_MULTI_MAX; }
+
+extern "C++" {
+static int mapped_multi(const zhip_mapped_args* args, uint32_t n, void* stream, bool dry) {
+    if (n < 2u || n > (uint32_t)ZHIP_MULTI_MAX)
+        return set_err(ZHIP_E_UNSUPPORTED, "zhip_decode_mapped_multi takes 2 .. zhip_multi_max() entries");
+    if (!args) return set_err(ZHIP_E_INVALID, "null args");
+    DecodeParams ps[ZHIP_MULTI_MAX];
+    int max_grid[ZHIP_MULTI_MAX];
+    for (uint32_t i = 0; i < n; ++i)  // arrival words and statuses are per launch
+        for (uint32_t j = 0; j < i; ++j)
+            if (args[i].d_workspace == args[j].d_workspace || args[i].d_status == args[j].d_status)
+                return set_err(ZHIP_E_UNSUPPORTED, "fused decodes must not share a workspace or status table");
+    for (uint32_t i = 0; i < n; ++i) {
+        const zhip_mapped_args& a = args[i];
+        bool empty;
+        const int rc = mapped_params(a.plan, a.src, a.src_size, a.out, a.d_chunks, a.n_chunks, a.d_sels, a.d_status,
+                                     a.d_workspace, a.d_errflag, a.d_index_chunks, a.n_index, a.d_index_status,
+                                     a.decode_flags, a.pred, a.d_rowmap, ps[i], empty, dry);
+        if (rc != ZHIP_OK) return rc;
+        if (empty) return set_err(ZHIP_E_UNSUPPORTED, "an empty decode cannot be fused");
+        max_grid[i] = a.plan->max_grid;
+    }
+    const int rc = launch_decode_multi(ps, max_grid, n, static_cast<hipStream_t>(stream), dry);
+    if (rc == ZHIP_E_UNSUPPORTED)
+        return set_err(rc, "not fusable: every entry must take the same production k_decode_il");
+    if (rc != ZHIP_OK) return set_err(rc, std::string("launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return ZHIP_OK;
+}
+}
+
+int zhip_decode_mapped_multi(const zhip_mapped_args* args, uint32_t n, void* stream) {
+    return mapped_multi(args, n, stream, false);
+}
+
+int zhip_decode_mapped_multi_check(const zhip_mapped_args* args, uint32_t n) {
+    return mapped_multi(args, n, nullptr, true);
 }
 
 int zhip_encode(const zhip_plan* plan, const void* arr, void* dst, const zhip_chunk* d_chunks, uint32_t n_chunks,

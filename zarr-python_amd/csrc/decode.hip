@@ -686,6 +686,50 @@ static KernelFn pick_pair_kernel(const Launch& L, int nu) {
     return select_pair_kernel(L.crc, L.item, L.swap, nu == 2 ? kPairTwo : kPairSingle);
 }
 
+// The production rule of the whole-row layouts, arm by arm (launch_row_units
+// reads them top to bottom; launch_decode_multi admits only the last).
+// lead4 / lead8: chunks of one unit of at most 16 KiB
+static bool takes_lead4(const Launch& L) {
+    return L.p.nseg == 1u && L.p.E <= 4u * kWgStride && g_tune_arm != kArmNoLead4;
+}
+
+// lead: inner chunks without a CRC under checked shard indexes
+static bool takes_lead(const Launch& L) { return !L.crc && L.p.n_idx; }
+
+// chunks of a multiple of 8 x 32 KiB: interleaved steps in groups of
+// eight workgroups (k_decode_il, see decode_rows.hip) -- graph-timed
+// 26.4 vs 27.8 us on the headline; groups of four lose to the pair
+// kernel at C4 (profiles/r03/il/).  kTuneIl / kTuneNoIl force.
+static bool takes_interleaved(const Launch& L) {
+    const DecodeParams& p = L.p;
+    return p.il_S != 0 && L.crc && !(L.tune & (kTuneNoIl | kTuneSkipCrc | kTuneSingle | kTuneDuo)) &&
+           ((L.tune & kTuneIl) || p.il_S >= 8u);
+}
+
+// grids of at most kIlwMaxUnits units (2 per CU: the N = 4 / 8 shares of
+// the strong-scaled headline) with fewer chunks than CUs: half units of
+// 16 KiB (k_decode_ilh, two workgroups per unit) publishing through the
+// look-back finalizer -- graph-timed 8.39 vs 9.77 us (k_decode_ilw512)
+// at the N = 8 share, 10.73 vs 11.03 at N = 4 (profiles/r06/a/).
+// (Tuning build: arm 0 only; arm 58 / 49 keep k_decode_ilw512.)
+static bool takes_ilh(const Launch& L, bool il) {
+    const DecodeParams& p = L.p;
+    return il && p.ilh_klane && p.n_units <= kIlwMaxUnits && L.lb_ok && p.nseg <= 32u &&
+           (g_tune_arm == kArmProduction || g_tune_arm == kArmIlhProduction) && (L.tune & ~kTuneStamp) == 0;
+}
+
+// otherwise 512 lanes per unit, four blocks per lane (k_decode_ilw,
+// decode_rows.hip) -- graph-timed 8.8 vs 9.4 us at the N = 8 share, 10.3
+// vs 11.0 at N = 4; 14.6 vs 16.5 for k_decode_il at N = 2
+// (profiles/r05/f/).  (Tuning build: any arm keeps k_decode_il.)
+static bool takes_ilw512(const Launch& L, bool il) {
+    const DecodeParams& p = L.p;
+    return il && p.ilw_nt == 512u && p.n_units <= kIlwMaxUnits &&
+           (g_tune_arm == kArmProduction || g_tune_arm == kArmRowMap || g_tune_arm == kArmIlw512Small ||
+            ((g_tune_arm == kArmSplitPub || g_tune_arm == kArmLookBack) && p.aff_ok)) &&
+           (L.tune & ~kTuneStamp) == 0;
+}
+
 // Whole-row layouts with a row map, 32 KiB units: one workgroup per unit,
 // half unit or pair of units, non-persistent.  The production rule reads top
 // to bottom: lead4 / lead8, lead, ilh, ilw512, il, duo, pair.
@@ -693,36 +737,17 @@ static int launch_row_units(const Launch& L) {
     const DecodeParams& p = L.p;
     const uint32_t tune = L.tune;
     const bool crc = L.crc;
-    if (p.nseg == 1u && p.E <= 4u * kWgStride && g_tune_arm != kArmNoLead4) return launch_lead4(L);
-    if (!crc && p.n_idx) return launch_lead(L);
-    // chunks of a multiple of 8 x 32 KiB: interleaved steps in groups of
-    // eight workgroups (k_decode_il, see decode_rows.hip) -- graph-timed
-    // 26.4 vs 27.8 us on the headline; groups of four lose to the pair
-    // kernel at C4 (profiles/r03/il/).  kTuneIl / kTuneNoIl force.
-    const bool il = p.il_S != 0 && crc && !(tune & (kTuneNoIl | kTuneSkipCrc | kTuneSingle | kTuneDuo)) &&
-                    ((tune & kTuneIl) || p.il_S >= 8u);
+    if (takes_lead4(L)) return launch_lead4(L);
+    if (takes_lead(L)) return launch_lead(L);
+    const bool il = takes_interleaved(L);
 #if ZHIP_TUNING
     int rc;
     if (launch_row_arm(L, il, rc)) return rc;
 #endif
-    // grids of at most kIlwMaxUnits units (2 per CU: the N = 4 / 8 shares of
-    // the strong-scaled headline) with fewer chunks than CUs: half units of
-    // 16 KiB (k_decode_ilh, two workgroups per unit) publishing through the
-    // look-back finalizer -- graph-timed 8.39 vs 9.77 us (k_decode_ilw512)
-    // at the N = 8 share, 10.73 vs 11.03 at N = 4 (profiles/r06/a/).
-    // (Tuning build: arm 0 only; arm 58 / 49 keep k_decode_ilw512.)
-    if (il && p.ilh_klane && p.n_units <= kIlwMaxUnits && L.lb_ok && p.nseg <= 32u &&
-        (g_tune_arm == kArmProduction || g_tune_arm == kArmIlhProduction) && (tune & ~kTuneStamp) == 0)
+    if (takes_ilh(L, il))
         return fire(select_ilh_kernel(L.item, L.swap, true, p.aff_ok != 0), "k_decode_ilh",
                     unit_grid(p, 2u * p.n_units), kThreads, p, L.stream);
-    // otherwise 512 lanes per unit, four blocks per lane (k_decode_ilw,
-    // decode_rows.hip) -- graph-timed 8.8 vs 9.4 us at the N = 8 share, 10.3
-    // vs 11.0 at N = 4; 14.6 vs 16.5 for k_decode_il at N = 2
-    // (profiles/r05/f/).  (Tuning build: any arm keeps k_decode_il.)
-    if (il && p.ilw_nt == 512u && p.n_units <= kIlwMaxUnits &&
-        (g_tune_arm == kArmProduction || g_tune_arm == kArmRowMap || g_tune_arm == kArmIlw512Small ||
-         ((g_tune_arm == kArmSplitPub || g_tune_arm == kArmLookBack) && p.aff_ok)) &&
-        (tune & ~kTuneStamp) == 0) {
+    if (takes_ilw512(L, il)) {
         // (tuning arms, whole-chunk reads: 49 the split publication, 58 the
         // look-back finalizer)
         const IlwForm form = g_tune_arm == kArmSplitPub ? kIlw512Split
@@ -831,18 +856,62 @@ static int launch_tile_groups(const Launch& L) {
 // The kernel of a launch, by layout: whole-row units, persistent rows, the
 // tile kernels of transposed layouts (tile4, tile pairs, grouped tiles,
 // persistent tile), else the generic persistent k_decode.
-int launch_decode(const DecodeParams& p, hipStream_t stream, int max_grid) {
+static Launch make_launch(const DecodeParams& p, hipStream_t stream, int max_grid) {
     const bool crc = (p.lflags & ZHIP_LF_CRC) != 0;
     const bool lb_ok = p.n_chunks < (uint32_t)(max_grid / 8);  // max_grid arrives as CUs * 8
     if (g_tune_max_grid > 0) max_grid = g_tune_max_grid;
-    const Launch L = {p, stream, max_grid, ZHIP_TUNING ? p.tune : 0u, lb_ok, crc, (p.lflags & ZHIP_LF_SWAP) != 0,
-                      p.g.itemsize};
+    return {p, stream, max_grid, ZHIP_TUNING ? p.tune : 0u, lb_ok, crc, (p.lflags & ZHIP_LF_SWAP) != 0,
+            p.g.itemsize};
+}
+
+static bool takes_row_units(const Launch& L) {
+    const DecodeParams& p = L.p;
     // (the kTunePersist arm never applies to a launch carrying fused index
     // checks of CRC-free inner chunks: only k_decode_lead carries those)
-    const bool lead_launch = !crc && p.n_idx != 0;
-    if (p.rows && p.rowmap && p.seg == (uint32_t)kWgStride * kDefaultBlocks &&
-        (!(L.tune & kTunePersist) || lead_launch))
-        return launch_row_units(L);
+    const bool lead_launch = !L.crc && p.n_idx != 0;
+    return p.rows && p.rowmap && p.seg == (uint32_t)kWgStride * kDefaultBlocks &&
+           (!(L.tune & kTunePersist) || lead_launch);
+}
+
+// launch_decode would fire the production k_decode_il for L: the row-unit
+// rule down to its `il` arm (tuning build: the production arm, no ablation bit)
+static bool takes_plain_il(const Launch& L) {
+    if (!takes_row_units(L) || takes_lead4(L) || takes_lead(L)) return false;
+    const bool il = takes_interleaved(L);
+    if (!il || takes_ilh(L, il) || takes_ilw512(L, il)) return false;
+    return g_tune_arm == kArmProduction && L.tune == 0u;
+}
+
+uint64_t g_launch_count = 0;
+
+int launch_decode_multi(const DecodeParams* ps, const int* max_grid, uint32_t n, hipStream_t stream, bool dry) {
+    if (n < 2u || n > (uint32_t)ZHIP_MULTI_MAX) return ZHIP_E_UNSUPPORTED;
+    MultiParams m{};
+    MultiFn fn = nullptr;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const Launch L = make_launch(ps[i], stream, max_grid[i]);
+        if (!takes_plain_il(L)) return ZHIP_E_UNSUPPORTED;
+        MultiFn f = select_il_multi_kernel(L.crc, L.item, L.swap, ps[i].aff_ok != 0);
+        if (!f || (i && f != fn)) return ZHIP_E_UNSUPPORTED;  // one instantiation for the whole grid
+        fn = f;
+        const uint32_t grid = unit_grid(ps[i], ps[i].n_units);
+        if (grid == 0) return ZHIP_E_UNSUPPORTED;
+        m.q[i] = ps[i];
+        m.g0[i] = (uint32_t)total;
+        total += grid;
+        if (total > 0x7FFFFFFFull) return ZHIP_E_UNSUPPORTED;
+    }
+    for (uint32_t i = n; i <= (uint32_t)ZHIP_MULTI_MAX; ++i) m.g0[i] = (uint32_t)total;
+    m.n = n;
+    if (dry) return ZHIP_OK;  // (zhip_decode_mapped_multi_check: the admission alone)
+    return fire(fn, "k_decode_il", (uint32_t)total, kThreads, m, stream);  // (the same kernel body)
+}
+
+int launch_decode(const DecodeParams& p, hipStream_t stream, int max_grid) {
+    const Launch L = make_launch(p, stream, max_grid);
+    const bool crc = L.crc;
+    if (takes_row_units(L)) return launch_row_units(L);
     if (p.rows)
         return launch_persistent(L, select_rows_kernel(crc, L.item, L.swap, (int)(p.seg / kWgStride)), "k_decode_rows");
     if (p.tq >= 0 && p.tile4) return launch_tile4(L);
@@ -856,3 +925,4 @@ int launch_decode(const DecodeParams& p, hipStream_t stream, int max_grid) {
 }  // namespace zhip
 
 extern "C" const char* zhip_last_kernel(void) { return zhip::g_last_kernel; }
+extern "C" uint64_t zhip_launch_count(void) { return zhip::g_launch_count; }

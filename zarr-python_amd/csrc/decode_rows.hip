@@ -1361,23 +1361,24 @@ __device__ __forceinline__ void publish_lb(const DecodeParams& p, uint32_t c, ui
 //   check instead of written to the sink; 1 = write-through (sc1: no dirty
 //   lines left in L2 at the kernel's end), 2 = nontemporal (the production
 //   policy, isolating the store form)
-template <bool CRC, int ITEM, bool SWAP, bool LEAN = false, bool CF = false, int LM = 0, bool TUNE = false,
-          int PUB = 3, bool AFF = false, int PRIO = 0, int STW = 0>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(LM == 2 ? 6 : 4, LM == 2 ? 6 : 4)))
-void k_decode_il(const DecodeParams p) {
+//
+// The body is il_body: workgroup gx of a grid of G workgroups over the launch
+// p.  k_decode_il runs it on its own grid; k_decode_il_multi runs several
+// launches' grids back to back in one (each workgroup on its launch's
+// parameters, with its index and grid size in that launch).
+template <bool CRC, int ITEM, bool SWAP, bool LEAN, bool CF, int LM, bool TUNE, int PUB, bool AFF, int PRIO, int STW>
+__device__ __forceinline__ void il_body(const DecodeParams& p, const uint32_t gx, const uint32_t G) {
     constexpr int K = kDefaultBlocks;
     if constexpr ((PRIO & 6) != 0) __builtin_amdgcn_s_setprio(3);
     __shared__ uint32_t s_tab[CRC ? kPairTabWords : 1];
     __shared__ uint32_t s_mul[CRC && LM == 0 ? 12 * kThreads : 1];
     __shared__ uint32_t s_red[2][kThreads / 64];
     const int t = threadIdx.x;
-    const uint32_t G = gridDim.x;
     // (PRIO bit 3, tuning arm 57: XCD-contiguous eighths of the grid -- the
     // dispatcher's XCD blockIdx % 8 takes workgroups [x G/8, (x + 1) G/8);
     // -0.14 to -0.56 us on one box, +0.4 to +0.8 us on another in four
     // interleaved pairs, profiles/r05/ai/: not adopted)
-    const uint32_t g = ((PRIO & 8) != 0 && (G & 7u) == 0u) ? (blockIdx.x & 7u) * (G >> 3) + (blockIdx.x >> 3)
-                                                           : blockIdx.x;
+    const uint32_t g = ((PRIO & 8) != 0 && (G & 7u) == 0u) ? (gx & 7u) * (G >> 3) + (gx >> 3) : gx;
     const uint32_t expected = p.g.nbytes + (CRC ? 4u : 0u);
     const uint8_t* zero = reinterpret_cast<const uint8_t*>(g_rows_zero);
     uint32_t c, r, st0;
@@ -1609,6 +1610,41 @@ void k_decode_il(const DecodeParams p) {
     //    this kernel only then), the first block prefetched with the data
     if constexpr (CRC)
         for (uint32_t j = g; j < p.n_idx; j += G) verify_index_pair(p, j, t, kix, s_tab, s_red[1], j == g, ipre);
+}
+
+template <bool CRC, int ITEM, bool SWAP, bool LEAN = false, bool CF = false, int LM = 0, bool TUNE = false,
+          int PUB = 3, bool AFF = false, int PRIO = 0, int STW = 0>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(LM == 2 ? 6 : 4, LM == 2 ? 6 : 4)))
+void k_decode_il(const DecodeParams p) {
+    il_body<CRC, ITEM, SWAP, LEAN, CF, LM, TUNE, PUB, AFF, PRIO, STW>(p, blockIdx.x, gridDim.x);
+}
+
+// k_decode_il_multi: the grids of m.n independent k_decode_il launches (other
+// sources, outs, workspaces and status tables) back to back in ONE grid:
+// workgroups [g0[i], g0[i + 1]) run il_body on launch i's parameters as that
+// launch's workgroups 0 .. G_i - 1.  The dispatcher hands workgroups out in
+// index order, so launch i + 1's first workgroups take the CU slots launch i's
+// last ones free: one ramp and one tail per fused grid instead of one per
+// launch, and no kernel boundary between them.  The launch is found with
+// scalar compares (no division); its parameter block is read through a scalar
+// base like k_decode_il's own.  Production forms only (select_il_kernel's).
+template <bool CRC, int ITEM, bool SWAP, bool AFF>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_decode_il_multi(const MultiParams m) {
+    const uint32_t b = blockIdx.x;
+    uint32_t i = 0;
+#pragma unroll
+    for (uint32_t k = 1; k < ZHIP_MULTI_MAX; ++k) i += (k < m.n && b >= m.g0[k]) ? 1u : 0u;
+    il_body<CRC, ITEM, SWAP, false, false, 0, false, 3, AFF, AFF ? 4 : 0, 0>(m.q[i], b - m.g0[i],
+                                                                                m.g0[i + 1] - m.g0[i]);
+}
+
+MultiFn select_il_multi_kernel(bool crc, int item, bool swap, bool aff) {  // select_il_kernel's forms
+    return for_item(item, swap, [&](auto t) -> MultiFn {
+        using T = decltype(t);
+        if (!crc) return k_decode_il_multi<false, T::item, T::swap, false>;
+        return aff ? k_decode_il_multi<true, T::item, T::swap, true> : k_decode_il_multi<true, T::item, T::swap, false>;
+    });
 }
 
 #if ZHIP_TUNING

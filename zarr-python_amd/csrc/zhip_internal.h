@@ -182,6 +182,21 @@ struct DecodeParams {
     uint64_t pred_base, pred_outer, pred_inner;
 };
 
+// The one argument of k_decode_il_multi (zhip_decode_mapped_multi): the
+// parameters of n independent k_decode_il launches and the prefix sums of
+// their grids -- workgroups [g0[i], g0[i + 1]) of the fused grid are launch
+// i's.  ZHIP_MULTI_MAX is what fits a 4 KiB kernel-argument segment.
+#define ZHIP_MULTI_MAX 3
+template <int N>
+struct MultiParamsN {
+    DecodeParams q[N];
+    uint32_t g0[N + 1];
+    uint32_t n;
+};
+using MultiParams = MultiParamsN<ZHIP_MULTI_MAX>;
+static_assert(sizeof(MultiParams) <= 4096 && sizeof(MultiParamsN<ZHIP_MULTI_MAX + 1>) > 4096,
+              "ZHIP_MULTI_MAX: the DecodeParams that fit a 4 KiB kernel-argument segment");
+
 // n / d == (n * m) >> s for 0 <= n < 2^31 (host side; fdiv_apply on the device)
 inline zhip_fdiv make_fdiv(uint32_t d) {
     zhip_fdiv f;
@@ -433,6 +448,12 @@ struct PackParams {
 };
 
 int launch_decode(const DecodeParams& p, hipStream_t stream, int max_grid);
+// n independent launches in one grid (k_decode_il_multi); ZHIP_E_UNSUPPORTED,
+// with nothing launched, unless each would take the production k_decode_il
+// arm and all the same instantiation.  max_grid: per launch, as launch_decode's;
+// dry: the admission alone, no launch
+int launch_decode_multi(const DecodeParams* ps, const int* max_grid, uint32_t n, hipStream_t stream, bool dry);
+extern uint64_t g_launch_count;  // zhip_launch_count: kernel launches issued by fire / launch_decode_multi
 int launch_encode(const EncodeParams& p, hipStream_t stream, int max_grid);
 int launch_shard_pack(const PackParams& p, uint32_t n_shards, hipStream_t stream);
 int launch_dv_check(const zhip_dv_ref* d_refs, uint32_t n_refs, hipStream_t stream);
@@ -443,6 +464,7 @@ int debug_stamps(uint64_t* host_out, uint32_t n_wg);
 // launch_encode (decode.hip / encode.hip) call them.
 using KernelFn = void (*)(const DecodeParams);
 using EncodeFn = void (*)(const EncodeParams);
+using MultiFn = void (*)(const MultiParams);
 
 // select_pair_kernel: the two-unit kernel, its tuning forms and the kernels
 // of its family (the values past kPairTwo exist in the tuning build only,
@@ -497,6 +519,7 @@ KernelFn select_rows_kernel(bool crc, int item, bool swap, int k);
 KernelFn select_pair_kernel(bool crc, int item, bool swap, PairForm form);
 KernelFn select_duo_kernel(bool crc, int item, bool swap);
 KernelFn select_il_kernel(bool crc, int item, bool swap, bool aff);
+MultiFn select_il_multi_kernel(bool crc, int item, bool swap, bool aff);  // k_decode_il_multi, the same forms
 KernelFn select_ilw_kernel(int item, bool swap, IlwForm form, bool lmr, bool aff);
 KernelFn select_ilh_kernel(int item, bool swap, bool lb, bool aff);
 #if ZHIP_TUNING

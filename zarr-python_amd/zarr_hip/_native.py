@@ -144,6 +144,18 @@ class Predict(ctypes.Structure):
                 ("per", ctypes.c_uint32), ("_pad", ctypes.c_uint32)]
 
 
+class MappedArgs(ctypes.Structure):
+    """zhip_mapped_args (include/zarrhip.h): one zhip_decode_mapped call."""
+
+    _fields_ = [("plan", ctypes.c_void_p), ("src", ctypes.c_void_p), ("src_size", ctypes.c_uint64),
+                ("out", ctypes.c_void_p), ("d_chunks", ctypes.c_void_p), ("n_chunks", ctypes.c_uint32),
+                ("_pad0", ctypes.c_uint32), ("d_sels", ctypes.c_void_p), ("d_status", ctypes.c_void_p),
+                ("d_workspace", ctypes.c_void_p), ("d_errflag", ctypes.c_void_p),
+                ("d_index_chunks", ctypes.c_void_p), ("n_index", ctypes.c_uint32), ("_pad1", ctypes.c_uint32),
+                ("d_index_status", ctypes.c_void_p), ("decode_flags", ctypes.c_uint32), ("_pad2", ctypes.c_uint32),
+                ("pred", ctypes.POINTER(Predict)), ("d_rowmap", ctypes.c_void_p)]
+
+
 # zhip_piece (include/zarrhip.h)
 PIECE_DT = np.dtype([("host", "<u8"), ("nbytes", "<u8"), ("dst_off", "<u8"), ("flags", "<u8"),
                      ("file_off", "<u8")])
@@ -237,6 +249,14 @@ def lib():
     L.zhip_decode_predicted.restype = ctypes.c_int
     L.zhip_decode_mapped.argtypes = L.zhip_decode_predicted.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_void_p]
     L.zhip_decode_mapped.restype = ctypes.c_int
+    L.zhip_multi_max.argtypes = []
+    L.zhip_multi_max.restype = ctypes.c_uint32
+    L.zhip_decode_mapped_multi.argtypes = [ctypes.POINTER(MappedArgs), ctypes.c_uint32, ctypes.c_void_p]
+    L.zhip_decode_mapped_multi.restype = ctypes.c_int
+    L.zhip_decode_mapped_multi_check.argtypes = [ctypes.POINTER(MappedArgs), ctypes.c_uint32]
+    L.zhip_decode_mapped_multi_check.restype = ctypes.c_int
+    L.zhip_launch_count.argtypes = []
+    L.zhip_launch_count.restype = ctypes.c_uint64
     L.zhip_rows_map_len.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     L.zhip_rows_map_len.restype = ctypes.c_uint64
     L.zhip_rows_map.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,

@@ -16,6 +16,7 @@ repeated reads of the same selection) can re-launch without re-planning.
 from __future__ import annotations
 
 import asyncio
+import ctypes
 import os
 import threading
 import warnings
@@ -307,13 +308,35 @@ class DecodeLaunch:
     def launch(self, stream: int | None = None) -> None:
         if self.n == 0:
             return
+        self._issue(self._begin(), _stream_handle(self.device) if stream is None else stream)
+
+    def _begin(self) -> int:
+        """The host side of one launch: the count, and the decode flags with
+        this launch's deferred-verdict bank.  (launch() and launch_fused()
+        issue what it returns.)"""
         LAUNCHES[0] += 1
-        s = _stream_handle(self.device) if stream is None else stream
-        out_ptr = self.out.data_ptr() if self.out is not None else None
         # deferred CRC verdicts (zarrhip.h): consecutive launches publish into
         # alternate workspace banks (also while captured into a graph)
         flags = self.flags | (N.DF_BANK1 if self._bank else 0)
         self._bank ^= 1
+        return flags
+
+    def mapped_args(self, flags: int) -> "N.MappedArgs":
+        """This launch as one entry of zhip_decode_mapped_multi."""
+        a = N.MappedArgs()
+        a.plan, a.src, a.src_size = self.plan.handle, self.src.data_ptr(), self.src_size
+        a.out = self.out.data_ptr() if self.out is not None else None
+        a.d_chunks, a.n_chunks, a.d_sels = self.p_chunks, self.n, self.p_sels
+        a.d_status, a.d_workspace, a.d_errflag = self.p_status, self.p_ws, self.p_err
+        a.d_index_chunks, a.n_index, a.d_index_status = self.p_idx_chunks, self.n_idx, self.p_idx_status
+        a.decode_flags = flags
+        if self.predict is not None:
+            a.pred = ctypes.pointer(self.predict)
+        a.d_rowmap = self.p_rowmap
+        return a
+
+    def _issue(self, flags: int, s: int) -> None:
+        out_ptr = self.out.data_ptr() if self.out is not None else None
         src = self.src.data_ptr()
         if self.p_rowmap is not None:
             N.check(N.lib().zhip_decode_mapped(
@@ -537,16 +560,121 @@ class DecodeProgram:
         return tuple(out)
 
 
+@dataclass(frozen=True)
+class FuseEntry:
+    """What fuse_groups reads of one launch of a sequence."""
+
+    launch: Any            # the DecodeLaunch (compared by identity)
+    device: Any
+    single: bool           # exactly one mapped data launch: no index launch, no pending staging
+    out_range: tuple | None  # [lo, hi) addresses the launch may write
+    group: Any = None      # the ProgramGroup it belongs to (selections disjoint by construction)
+
+
+def fuse_groups(entries: list, max_n: int) -> list:
+    """Cut a launch sequence into runs that may share one kernel launch
+    (zhip_decode_mapped_multi): lists of indices into ``entries``, in order,
+    covering every entry once.  Consecutive entries join a run only while
+    every member is a single mapped data launch, all are distinct launches
+    (one launch's arrival words cannot serve two grids at once) on one device,
+    their out ranges are pairwise disjoint -- or they belong to one
+    ProgramGroup -- and the run holds at most ``max_n``.  Nothing is ordered
+    inside a fused launch, so anything else stays a launch of its own."""
+    runs: list = []
+    cur: list = []
+
+    def joins(e) -> bool:
+        if not cur or len(cur) >= max_n or not e.single:
+            return False
+        for i in cur:
+            o = entries[i]
+            if not o.single or o.launch is e.launch or o.device != e.device:
+                return False
+            if e.group is not None and o.group is e.group:
+                continue
+            a, b = o.out_range, e.out_range
+            if a is None or b is None or (a[0] < b[1] and b[0] < a[1]):
+                return False
+        return True
+
+    for i, e in enumerate(entries):
+        if joins(e):
+            cur.append(i)
+        else:
+            if cur:
+                runs.append(cur)
+            cur = [i]
+    if cur:
+        runs.append(cur)
+    return runs
+
+
+def _out_range(out) -> tuple | None:
+    """[lo, hi) addresses of a device tensor's elements."""
+    if out is None:
+        return None
+    lo = out.data_ptr()
+    if out.numel() == 0:
+        return (lo, lo)
+    span = 1 + sum((n - 1) * abs(st) for n, st in zip(out.shape, out.stride()))
+    return (lo, lo + span * out.element_size())
+
+
+def _fuse_entry(prog, group=None) -> FuseEntry:
+    """A program of a launch sequence as fuse_groups sees it."""
+    d = getattr(prog, "data", None)
+    single = (isinstance(prog, DecodeProgram) and prog.index is None and prog.pending is None and
+              isinstance(d, DecodeLaunch) and d.n > 0 and d.p_rowmap is not None)
+    if not single:
+        return FuseEntry(d if d is not None else prog, getattr(d, "device", None), False, None, group)
+    return FuseEntry(d, d.device, True, _out_range(d.out), group)
+
+
+_MULTI_MAX = [0]
+
+
+def multi_max() -> int:
+    """zhip_multi_max(): the most launches one fused launch takes."""
+    if not _MULTI_MAX[0]:
+        _MULTI_MAX[0] = int(N.lib().zhip_multi_max())
+    return _MULTI_MAX[0]
+
+
+def launch_fused(programs: list, stream: int | None = None) -> bool:
+    """One run of fuse_groups in ONE kernel launch (zhip_decode_mapped_multi).
+    Per program everything is as in its own launch(): the freshness check, the
+    launch count, the deferred-verdict bank.  Where the library declines
+    (ZHIP_E_UNSUPPORTED: the launches would not all take the same production
+    k_decode_il) the same launches are issued one by one; returns whether
+    they shared a launch."""
+    for p in programs:
+        p.check_fresh()
+    launches = [p.data for p in programs]
+    flags = [d._begin() for d in launches]
+    s = _stream_handle(launches[0].device) if stream is None else stream
+    args = (N.MappedArgs * len(launches))(*[d.mapped_args(f) for d, f in zip(launches, flags)])
+    rc = N.lib().zhip_decode_mapped_multi(args, len(launches), s)
+    if rc == N.E_UNSUPPORTED:
+        for d, f in zip(launches, flags):
+            d._issue(f, s)
+        return False
+    N.check(rc, "zhip_decode_mapped_multi")
+    return True
+
+
 class ProgramGroup:
     """The planned read of a batch whose items carry different chunk specs
     (spec_groups): one DecodeProgram per spec group, all over the same out
     (the groups' out selections are disjoint), launched back to back on one
-    stream; results come back in the batch's item order."""
+    stream -- neighbours that qualify in one kernel launch (fuse_groups);
+    results come back in the batch's item order."""
 
     def __init__(self, programs: list, groups: list, n_items: int):
         self.programs = programs
         self.groups = groups
         self.n_items = n_items
+        self._runs = None  # fuse_groups' cut of the programs
+        self._declined: set = set()  # runs the library would not fuse
 
     @property
     def data_launches(self) -> list:
@@ -568,8 +696,24 @@ class ProgramGroup:
             p.check_fresh()
 
     def launch(self, stream: int | None = None) -> None:
-        for p in self.programs:
-            p.launch(stream)
+        progs = self.programs
+        if len(progs) < 2:
+            for p in progs:
+                p.launch(stream)
+            return
+        runs = self._runs
+        if runs is None:
+            runs = fuse_groups([_fuse_entry(p, self) for p in progs], multi_max())
+            if all(getattr(p, "pending", None) is None for p in progs):
+                self._runs = runs  # (staged bytes all landed: the cut no longer changes)
+        for run in runs:
+            key = tuple(run)
+            if len(run) > 1 and key not in self._declined:
+                if not launch_fused([progs[i] for i in run], stream):
+                    self._declined.add(key)
+            else:
+                for i in run:
+                    progs[i].launch(stream)
 
     def retarget(self, out) -> None:
         for p in self.programs:
@@ -652,20 +796,31 @@ class ReadGraph:
     """A read loop captured once as a hipGraph and replayed with one launch.
 
     ``programs`` are planned reads (``prepare_read``); the graph holds
-    ``repeats`` launches cycling over them, in order, on one stream.  Replaying
-    it does exactly the work of the eager loop (every launch a full decode with
-    CRC verification and statuses), without one host-side launch per batch —
+    ``repeats`` decodes cycling over them on one stream.  Replaying it does
+    exactly the work of the eager loop (every decode a full one with CRC
+    verification and statuses), without one host-side launch per batch —
     the HIP-graph counterpart of re-issuing the same read in a data-loader
-    loop.  Statuses accumulate in each program's device tables; call
+    loop.  The programs are replayed in order, except that independent
+    neighbours may share a kernel launch (``fuse``, the default): up to
+    ``zhip_multi_max()`` consecutive, different programs on one device, each a
+    single mapped data launch, whose outs do not overlap (``fuse_groups``)
+    run as one grid of k_decode_il where each alone would take that kernel
+    (``zhip_decode_mapped_multi``); inside such a launch nothing is ordered.
+    Everything else -- the same program twice, programs sharing an out,
+    programs with an index launch -- keeps a launch of its own, in order, so
+    the later write to a shared out still wins.  ``fuse=False`` captures one
+    launch per decode.  ``launches`` is the number of decode launches in the
+    graph.  Statuses accumulate in each program's device tables; call
     ``results()`` to raise like the reference after a replay.
     """
 
-    def __init__(self, programs: list, repeats: int, device=None):
+    def __init__(self, programs: list, repeats: int, device=None, fuse: bool = True):
         torch = _torch()
         if not programs or repeats < 1:
             raise ValueError("ReadGraph needs at least one program and one repeat")
         self.programs = list(programs)
         self.repeats = int(repeats)
+        self.fuse = bool(fuse)
         self.device = device if device is not None else self.programs[0].data.device
         self.graph = torch.cuda.CUDAGraph()
         self.stream = torch.cuda.Stream(self.device)
@@ -680,10 +835,19 @@ class ReadGraph:
         odd = any(c % 2 for c, ds in zip(counts, launches) for d in ds if d is not None and hasattr(d, "d_ws"))
         self._dv_refs = _dv_refs([d for ds in launches for d in ds if d is not None], self.device) if odd \
             else None
+        seq = [self.programs[i % len(self.programs)] for i in range(self.repeats)]
+        # (a lone program, or fuse=False: one launch per decode, today's capture)
+        runs = fuse_groups([_fuse_entry(p) for p in seq], multi_max()) if self.fuse and len(self.programs) > 1 \
+            else [[i] for i in range(len(seq))]
+        n0 = N.lib().zhip_launch_count()
         with torch.cuda.device(self.device):
             with torch.cuda.graph(self.graph, stream=self.stream):
-                for i in range(self.repeats):
-                    self.programs[i % len(self.programs)].launch()
+                for run in runs:
+                    if len(run) > 1:
+                        launch_fused([seq[i] for i in run])
+                    else:
+                        seq[run[0]].launch()
+                self.launches = int(N.lib().zhip_launch_count() - n0)
                 if self._dv_refs is not None:
                     N.check(N.lib().zhip_dv_check(self._dv_refs.data_ptr(), self._dv_refs.numel() // 32,
                                                   int(self.stream.cuda_stream)), "zhip_dv_check")
