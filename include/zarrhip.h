@@ -749,6 +749,16 @@ uint32_t zhip_emulate_chunk_crc_il(const zhip_plan *plan, const uint8_t *data);
  * A_1024 tables, per-(span, lane) constants); 0xFFFFFFFF when the plan has no
  * xw layout.  Test hook. */
 uint32_t zhip_emulate_chunk_crc_xw(const zhip_plan *plan, const uint8_t *data);
+/* The table image zhip_plan_upload would put on the device, built on the host
+ * (the emulations above read the same): which = 0 the row tables, 1 the tile
+ * tables.  Copies up to cap u32 words to out (may be null); returns the
+ * image's word count, 0 if the plan has no such image.  Test hook. */
+uint64_t zhip_plan_table_image(const zhip_plan *plan, int which, uint32_t *out, uint64_t cap);
+/* The images' regions in the library's declaration order (row image first,
+ * address order within each): returns their number n and writes up to cap
+ * values to out -- out[i] the word offset of region i in its image (0: absent,
+ * or the image's first region), out[n + i] its word count.  Test hook. */
+uint32_t zhip_plan_table_offsets(const zhip_plan *plan, uint64_t *out, uint32_t cap);
 uint32_t zhip_fdiv_eval(uint32_t n, uint32_t d);
 
 #ifdef __cplusplus

@@ -8,7 +8,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -37,62 +36,10 @@ int set_err(int code, const std::string& msg) {
             return set_err(ZHIP_E_HIP, std::string(#expr ": ") + hipGetErrorString(e_));  \
     } while (0)
 
-uint32_t g_T[256];      // standard byte table: A_1(v) = (v >> 8) ^ T[v & 255]
-uint8_t g_invtop[256];  // top byte of T[i] -> i
-std::once_flag g_once;
-
-void init_tables() {
-    for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (kPoly & (0u - (c & 1u)));
-        g_T[i] = c;
-    }
-    for (uint32_t i = 0; i < 256; ++i) g_invtop[g_T[i] >> 24] = (uint8_t)i;
-}
-
-// x^(8n) mod P
-uint32_t xpow8(uint64_t n) {
-    uint32_t p = kOne;
-    uint32_t b = kOne >> 8;  // x^8
-    while (n) {
-        if (n & 1) p = gf_mul(p, b);
-        b = gf_mul(b, b);
-        n >>= 1;
-    }
-    return p;
-}
-
-// x^-8 mod P: one inverse byte step applied to 1.
-uint32_t xinv8() {
-    const uint32_t s = kOne;
-    const uint32_t i = g_invtop[s >> 24];
-    return (((s ^ g_T[i]) & 0x00FFFFFFu) << 8) | i;
-}
-
-// x^(-8n) mod P = (x^-8)^n by square-and-multiply.
-uint32_t xpow8_inv(uint64_t n) {
-    uint32_t p = kOne;
-    uint32_t b = xinv8();
-    while (n) {
-        if (n & 1) p = gf_mul(p, b);
-        b = gf_mul(b, b);
-        n >>= 1;
-    }
-    return p;
-}
-
-void build_horner_stride(uint32_t* tab, uint64_t stride) {  // [op][slice][256], op k = A_(stride - 4k)
-    for (int op = 0; op < 4; ++op) {
-        const uint32_t x = xpow8(stride - 4u * op);
-        for (int sl = 0; sl < 4; ++sl)
-            for (uint32_t b = 0; b < 256; ++b) tab[op * 1024 + sl * 256 + b] = gf_mul(x, b << (8 * sl));
-    }
-}
-
-
 uint32_t crc_bytewise(const uint8_t* p, size_t n) {
+    const uint32_t* T = byte_tables().T;
     uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < n; ++i) c = (c >> 8) ^ g_T[(c ^ p[i]) & 255u];
+    for (size_t i = 0; i < n; ++i) c = (c >> 8) ^ T[(c ^ p[i]) & 255u];
     return ~c;
 }
 
@@ -114,69 +61,9 @@ __attribute__((target("sse4.2"))) uint32_t crc_sse42(const uint8_t* p, size_t n)
     return ~(uint32_t)c;
 }
 
-// k_decode_pair tables (kPairTab* layout): A4096 (A_stride) over 11/11/10-bit
-// slices of a word, and the byte slices of A4 that fold the four word
-// accumulators
-void build_pair_tables(uint32_t* tab, uint64_t stride = kWgStride) {
-    const uint32_t x = xpow8(stride);
-    for (uint32_t i = 0; i < 2048; ++i) {
-        tab[kPairT1 + i] = gf_mul(x, i);
-        tab[kPairT2 + i] = gf_mul(x, i << 11);
-    }
-    for (uint32_t i = 0; i < 1024; ++i) tab[kPairT3 + i] = gf_mul(x, i << 22);
-    const uint32_t x4 = xpow8(4);
-    for (int sl = 0; sl < 4; ++sl)
-        for (uint32_t b = 0; b < 256; ++b) tab[kPairA4 + sl * 256 + b] = gf_mul(x4, b << (8 * sl));
-}
-
-void build_horner(uint32_t* tab) {  // [op][slice][256], op k = A_(4096 - 4k)
-    for (int op = 0; op < 4; ++op) {
-        const uint32_t x = xpow8((uint64_t)kWgStride - 4u * op);
-        for (int sl = 0; sl < 4; ++sl)
-            for (uint32_t b = 0; b < 256; ++b) tab[op * 1024 + sl * 256 + b] = gf_mul(x, b << (8 * sl));
-    }
-}
-
 }  // namespace
 
 namespace zhip {
-// Source offset of every tile's first row in the stored chunk (tile index:
-// column block fastest, then row block, then the other dims, last fastest).
-std::vector<uint64_t> tile_bases(const zhip_plan& plan) {
-    const zhip_layout& L = plan.layout;
-    const uint64_t sq = plan.sstride[plan.tq];
-    std::vector<uint64_t> base(plan.t_per_chunk);
-    for (uint32_t ti = 0; ti < plan.t_per_chunk; ++ti) {
-        uint32_t r = ti;
-        const uint32_t cb = r % plan.n_cb;
-        r /= plan.n_cb;
-        const uint32_t qb = r % plan.n_qb;
-        r /= plan.n_qb;
-        uint64_t b = (uint64_t)qb * kTileRows * sq + (uint64_t)cb * kTileCols;
-        for (int d = L.ndim - 2; d >= 0; --d) {
-            if (d == plan.tq) continue;
-            b += (uint64_t)(r % (uint32_t)L.shape[d]) * plan.sstride[d];
-            r /= (uint32_t)L.shape[d];
-        }
-        base[ti] = b;
-    }
-    return base;
-}
-
-void fill_geom(Geom& g, const zhip_plan& plan) {
-    const zhip_layout& L = plan.layout;
-    g.ndim = L.ndim;
-    g.itemsize = L.itemsize;
-    for (int d = 0; d < ZHIP_MAX_DIMS; ++d) {
-        g.shape[d] = d < L.ndim ? L.shape[d] : 1;
-        g.ostride[d] = d < L.ndim ? L.out_stride[d] : 0;
-        g.dshape[d] = plan.dshape[d];
-    }
-    g.nbytes = (uint32_t)L.nbytes;
-    g.row_bytes = plan.row_bytes;
-    g.drow = plan.drow;
-}
-
 #if ZHIP_TUNING
 uint32_t g_tune_bits = 0;
 int g_tune_blocks = 0;
@@ -236,22 +123,7 @@ int zhip_device_count(void) {
 
 static void plan_affine(zhip_plan* p);
 
-// The one rule for k_decode_il / k_encode_il's wider interleave: groups of
-// S x 8 steps (S = 16 / 32) must tile the chunk's steps, and only plans whose
-// own groups are eight wide widen (il_S = 2 / 4: the tuning arms' narrow
-// groups keep theirs).  zhip_plan_upload builds a table set (off_il_s) for
-// every S that tiles; the launches and zhip_emulate_chunk_crc_il take the
-// widest.
-static bool il_tiles(const zhip_plan* p, uint32_t S) {
-    return p->il_S == 8u && ((uint64_t)p->nseg * kDefaultBlocks) % ((uint64_t)S * kDefaultBlocks) == 0;
-}
-
-static uint32_t il_widest(const zhip_plan* p) {
-    return il_tiles(p, 32u) ? 32u : il_tiles(p, 16u) ? 16u : p->il_S;
-}
-
 int zhip_plan_create(const zhip_layout* layout, zhip_plan** out) {
-    std::call_once(g_once, init_tables);
     if (!layout || !out) return set_err(ZHIP_E_INVALID, "null argument");
     const zhip_layout& L = *layout;
     if (L.ndim < 1 || L.ndim > ZHIP_MAX_DIMS) return set_err(ZHIP_E_UNSUPPORTED, "ndim must be 1..8");
@@ -360,487 +232,24 @@ int zhip_plan_create(const zhip_layout* layout, zhip_plan** out) {
         }
     }
     plan_affine(p);
+    plan_layout(*p);
     *out = p;
     return ZHIP_OK;
 }
 
-// Upload the constant tables to the current device (done once per plan).
+// Upload the constant tables to the current device (done once per plan and device).
 int zhip_plan_upload(zhip_plan* p) {
     if (!p) return set_err(ZHIP_E_INVALID, "null plan");
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (p->d_tables && p->device == dev) return ZHIP_OK;
-    // horner (4096) | kthread (256) | kunit (nseg) | kpair (nseg x 256): the
-    // per-lane constant kthread[t] * kunit[s] * c_inv of k_decode_pair, whose
-    // run ends then need no uniform multiply at all
-    const size_t n_old = 4096 + kThreads + p->nseg + (size_t)p->nseg * kThreads;
-    const size_t n_pair = kPairTabWords + (size_t)p->nseg * kThreads + kThreads;
-    const size_t n_il = p->il_S ? kPairTabWords + (size_t)p->nseg * kThreads + kThreads + kIlBasisWords : 0;
-    const size_t n_xw = p->xw_P ? kPairTabWords + (size_t)p->xw_P * 64 + kThreads : 0;
-    // k_decode_ilw regions (NT = 1024: tuning arms only; 512: the small-grid
-    // form of k_decode_il's layouts)
-    const bool ilw = (p->il_S == 8u || (ZHIP_TUNING && p->kblocks == (uint32_t)kDefaultBlocks &&
-                                        (p->layout.flags & ZHIP_LF_CRC) && !(p->layout.flags & ZHIP_LF_NO_WRITE))) &&
-                     p->nseg <= 256u;
-    size_t n_ilw[2] = {0, 0};
-    for (int i = ZHIP_TUNING ? 0 : 1; i < 2 && ilw; ++i) n_ilw[i] = kPairTabWords + (size_t)p->nseg * (1024u >> i) + kThreads;
-    const size_t n_ilh = (ilw && p->il_S == 8u && 2 * p->nseg <= 64u) ? (size_t)2 * p->nseg * kThreads : 0;
-    // k_decode_il's wider interleave (round 6): groups of 16 / 32 workgroups, the
-    // same tables and constants for strides S = 16 / 32 where the chunk's steps
-    // tile them (il_tiles; the decode and k_encode_il take the widest,
-    // il_widest; tuning arms 69 / 70 / 71 force 16 / 32 / 8).  Graph-timed on the
-    // headline: S = 32 25.49 / 25.33 us vs 25.76 / 25.76 for S = 8 in two
-    // interleaved pairs (profiles/r06/f/)
-    size_t n_ils[2] = {0, 0};
-    for (int i = 0; i < 2; ++i)
-        if (il_tiles(p, 16u << i)) n_ils[i] = n_il;
-    std::vector<uint32_t> h(n_old + n_pair + n_il + n_xw + n_ilw[0] + n_ilw[1] + n_ilh + n_ils[0] + n_ils[1]);
-    build_horner(h.data());
-    for (int t = 0; t < kThreads; ++t) h[4096 + t] = xpow8((uint64_t)kWgStride - 16u * t);
-    for (uint32_t s = 0; s < p->nseg; ++s) h[4096 + kThreads + s] = xpow8((uint64_t)s * p->seg);
-    for (uint32_t s = 0; s < p->nseg; ++s) {
-        const uint32_t ku = gf_mul(h[4096 + kThreads + s], p->c_inv);
-        for (int t = 0; t < kThreads; ++t)
-            h[4096 + kThreads + p->nseg + (size_t)s * kThreads + t] = gf_mul(h[4096 + t], ku);
-    }
-    // pair tables; the combined four-accumulator state sits 12 bytes later than
-    // the single-chain one, so the lane constants carry x^(-96)
-    p->off_pair = n_old;
-    build_pair_tables(h.data() + n_old);
-    const uint32_t c96 = xpow8_inv(12);
-    for (size_t i = 0; i < (size_t)p->nseg * kThreads; ++i)
-        h[n_old + kPairTabWords + i] = gf_mul(h[4096 + kThreads + p->nseg + i], c96);
-    for (int t = 0; t < kThreads; ++t)
-        h[n_old + kPairTabWords + (size_t)p->nseg * kThreads + t] = gf_mul(h[4096 + t], c96);
-    // k_decode_il: workgroup r of a chunk (group r / S, offset r % S) takes
-    // steps st_k = (r / S) S 8 + r % S + S k; lane t's chain over them (stride
-    // D = 4096 S) leaves word w of step st_0 multiplied by x^(8 D 8), so the
-    // lane constant x^(8 (E - p_0 + 4096 - 8 D)) c_inv x^(-96) gives every
-    // word at p the pair kernel's x^(8 (E - p + 4096)) c_inv (p_0 = E -
-    // 4096 (n_steps - st_0) + 16 t); exponents may be negative
-    auto build_il = [&](uint32_t* il, uint32_t il_S) {
-        const uint64_t D = (uint64_t)kWgStride * il_S;
-        build_pair_tables(il, D);
-        const int64_t n_steps = (int64_t)p->nseg * kDefaultBlocks, K = kDefaultBlocks, S = il_S;
-        for (uint32_t r = 0; r < p->nseg; ++r) {
-            const int64_t st0 = (int64_t)(r / S) * S * K + (int64_t)(r % S);
-            for (int t = 0; t < kThreads; ++t) {
-                const int64_t e = (int64_t)kWgStride * (n_steps - st0 + 1 - S * K) - 16 * t;
-                const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                il[kPairTabWords + (size_t)r * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-            }
-        }
-        // the fused index check (one 4 KiB step per lane) under A_D: its state
-        // is A_D(w) instead of A4096(w), so kthread11 times x^(-8(D - 4096))
-        const uint32_t back = xpow8_inv(D - (uint64_t)kWgStride);
-        for (int t = 0; t < kThreads; ++t)
-            il[kPairTabWords + (size_t)p->nseg * kThreads + t] =
-                gf_mul(h[n_old + kPairTabWords + (size_t)p->nseg * kThreads + t], back);
-        // the tables' bases (they are linear in the index): T1 / T2 / T3 at
-        // single bits, then the four A4 byte tables -- k_decode_ilc builds the
-        // tables in LDS from these 64 words instead of loading 24 KiB
-        uint32_t* bs = il + kPairTabWords + (size_t)p->nseg * kThreads + kThreads;
-        for (int b = 0; b < 11; ++b) bs[b] = il[kPairT1 + (1u << b)];
-        for (int b = 0; b < 11; ++b) bs[11 + b] = il[kPairT2 + (1u << b)];
-        for (int b = 0; b < 10; ++b) bs[22 + b] = il[kPairT3 + (1u << b)];
-        for (int j = 0; j < 4; ++j)
-            for (int b = 0; b < 8; ++b) bs[32 + 8 * j + b] = il[kPairA4 + 256 * j + (1u << b)];
-    };
-    p->off_il = 0;
-    if (p->il_S) {
-        p->off_il = n_old + n_pair;
-        build_il(h.data() + p->off_il, p->il_S);
-    }
-    p->off_xw = 0;
-    if (p->xw_P) {
-        // k_decode_xw: lane l of span r takes blocks p_k = lo + 8192 r + 1024 k
-        // + 16 l (k < 8); its chain (A_1024) leaves block 0 multiplied by
-        // x^(8 8192), so the constant x^(8 (E - p_0 + 4096 - 8192)) c_inv
-        // x^(-96) gives every word the pair kernel's frame
-        p->off_xw = n_old + n_pair + n_il;
-        uint32_t* xw = h.data() + p->off_xw;
-        build_pair_tables(xw, 1024);
-        const int64_t n_steps = (int64_t)p->nseg * kDefaultBlocks;
-        for (uint32_t r = 0; r < p->xw_P; ++r)
-            for (int l = 0; l < 64; ++l) {
-                const int64_t e = (int64_t)kWgStride * (n_steps - 2 * (int64_t)r - 1) - 16 * l;
-                const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                xw[kPairTabWords + (size_t)r * 64 + l] = gf_mul(gf_mul(xe, p->c_inv), c96);
-            }
-        // the fused index check under A_1024: state A_1024(w) instead of A4096(w)
-        const uint32_t fwd = xpow8((uint64_t)kWgStride - 1024u);
-        for (int t = 0; t < kThreads; ++t)
-            xw[kPairTabWords + (size_t)p->xw_P * 64 + t] =
-                gf_mul(h[n_old + kPairTabWords + (size_t)p->nseg * kThreads + t], fwd);
-    }
-    // k_decode_ilw: lane t of unit r (NT lanes) takes the blocks at 16 t + D k
-    // (D = 16 NT, k < 2048 / NT); its A_D chain leaves every word w at p
-    // multiplied by x^(8 (p_last + D - p)), so the lane constant
-    // x^(8 (4096 (n_steps - 8 r - 7) - 16 t)) c_inv x^(-96) gives the pair
-    // kernel's frame -- factored as F(r) G(t), G(t) = x^(-128 t)
-    size_t at = n_old + n_pair + n_il + n_xw;
-    for (int i = 0; i < 2; ++i) {
-        p->off_ilw[i] = 0;
-        if (!n_ilw[i]) continue;
-        const uint32_t NT = 1024u >> i;
-        const uint64_t D = 16ull * NT;
-        p->off_ilw[i] = at;
-        uint32_t* w = h.data() + at;
-        build_pair_tables(w, D);
-        const uint32_t xm128 = xpow8_inv(16);
-        std::vector<uint32_t> Gt(NT);
-        Gt[0] = kOne;
-        for (uint32_t t = 1; t < NT; ++t) Gt[t] = gf_mul(Gt[t - 1], xm128);
-        const uint64_t n_steps = (uint64_t)p->nseg * kDefaultBlocks;
-        for (uint32_t r = 0; r < p->nseg; ++r) {
-            const uint32_t F = gf_mul(gf_mul(xpow8(4096ull * (n_steps - 8ull * r - 7ull)), p->c_inv), c96);
-            for (uint32_t t = 0; t < NT; ++t) w[kPairTabWords + (size_t)r * NT + t] = gf_mul(F, Gt[t]);
-        }
-        const uint32_t back = xpow8_inv(D - (uint64_t)kWgStride);
-        for (int t = 0; t < kThreads; ++t)
-            w[kPairTabWords + (size_t)p->nseg * NT + t] =
-                gf_mul(h[n_old + kPairTabWords + (size_t)p->nseg * kThreads + t], back);
-        at += n_ilw[i];
-    }
-    // k_decode_ilh (small launches; tuning arm 41): lane t of half unit u = 2 r + h takes the
-    // sub-steps 8 r + 4 h + k (k < 4) at 16 t through A_4096; the constant
-    // x^(8 (4096 (n_steps - st0 - 3) - 16 t)) c_inv x^(-96), st0 = 8 r + 4 h
-    p->off_ilh = 0;
-    if (n_ilh) {
-        p->off_ilh = at;
-        const int64_t n_steps = (int64_t)p->nseg * kDefaultBlocks;
-        for (uint32_t uu = 0; uu < 2 * p->nseg; ++uu)
-            for (int t = 0; t < kThreads; ++t) {
-                const int64_t st0 = 8 * (int64_t)(uu >> 1) + 4 * (int64_t)(uu & 1u);
-                const int64_t e = (int64_t)kWgStride * (n_steps - st0 - 3) - 16 * t;
-                const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                h[at + (size_t)uu * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-            }
-        at += n_ilh;
-    }
-    for (int i = 0; i < 2; ++i) {  // S = 16 / 32
-        p->off_il_s[i] = 0;
-        if (!n_ils[i]) continue;
-        p->off_il_s[i] = at;
-        build_il(h.data() + at, 16u << i);
-        at += n_ils[i];
-    }
+    const std::vector<uint32_t> h = build_row_tables(*p);
     if (p->d_tables) (void)hipFree(p->d_tables);
     p->d_tables = nullptr;
     HIP_TRY(hipMalloc(&p->d_tables, h.size() * sizeof(uint32_t)));
     HIP_TRY(hipMemcpy(p->d_tables, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (p->tq >= 0) {
-        // thread t's Horner state lands at rel_t = (64 + t/16)*sq + 16*(t%16) from the
-        // tile base; shift every thread to REF, every tile from base+REF to R_c
-        const uint64_t sq = p->sstride[p->tq];
-        const uint64_t REF = (uint64_t)(kTileRows + 16) * sq + kTileCols;
-        const uint32_t T = p->t_per_chunk;
-        const std::vector<uint64_t> base = tile_bases(*p);
-        const zhip_layout& L = p->layout;
-        uint64_t maxb = 0;
-        for (uint32_t ti = 0; ti < T; ++ti) maxb = std::max(maxb, base[ti]);
-        const uint64_t Rc = maxb + REF;
-        const bool t4 = p->tile4 != 0;
-        const uint64_t step = p->tile4_step;
-        const size_t n_base = 4096 + kThreads + T;
-        const size_t n_t4 = t4 ? 1024 + (size_t)(T / 4) * kThreads + (size_t)T * 4 : 0;
-        const size_t n_g = p->gd >= 0 ? 1024 + (size_t)p->n_groups * (sizeof(GroupEnt) / 4) : 0;
-        // k_decode_tile4f: the four tiles of a group are the 256-byte pieces of
-        // 1 KiB of every stored row (step 256), so thread t's blocks (row t/4,
-        // 16 (t%4) + 64 n, n < 16) form one chain of stride 64 B
-        const bool t4f = t4 && step == (uint64_t)kTileCols && (L.flags & ZHIP_LF_CRC);
-        const size_t n_t4f = t4f ? kPairTabWords + (size_t)(T / 4) * kThreads : 0;
-        // k_decode_tile4w: wave w of a workgroup owns tile w; lane l its rows
-        // l/16 + 4 m (m < 16) at column block l % 16: one chain of stride 4 sq
-        const bool t4w = t4 && (L.flags & ZHIP_LF_CRC);
-        const size_t n_t4w = t4w ? kPairTabWords + (size_t)(T / 4) * kThreads : 0;
-        // k_decode_tilegw: the same chains for the four tiles of a group
-        const bool tgw = p->gd >= 0 && (L.flags & ZHIP_LF_CRC);
-        const size_t n_tgw = tgw ? kPairTabWords + (size_t)p->n_groups * kThreads : 0;
-        // the two-tile form of k_decode_tile4w (at most 32 workgroups per chunk:
-        // the one-word publication): lane constants only
-        const size_t n_t2w = (t4w && T % 2 == 0 && T / 2 <= 32) ? (size_t)(T / 2) * kThreads : 0;
-        const size_t n_t1w = (ZHIP_TUNING && t4w) ? (size_t)T * kThreads : 0;  // one tile per workgroup
-        // the two-tile form of k_decode_tilegw: two workgroups per group of four
-        const size_t n_tg2w = tgw ? (size_t)p->n_groups * 2 * kThreads : 0;
-        // the two-tile form of k_encode_tile4 (CRC, at most 32 workgroups per chunk)
-        const size_t n_t2e = (t4 && (L.flags & ZHIP_LF_CRC) && T % 2 == 0 && T / 2 <= 32) ? (size_t)(T / 2) * kThreads : 0;
-        // (tuning builds: the tile-pair decode, arm 39 -- 29.8-30.0 vs 29.2-29.4 us
-        // for the grouped kernel on C3 in 128^3 chunks, profiles/r05/q/)
-        const size_t n_t2 = (ZHIP_TUNING && p->tile2) ? kPairTabWords + (size_t)T * 4 + (size_t)(T / 2) * kThreads : 0;
-        const size_t n_tgl = (ZHIP_TUNING && tgw) ? (size_t)p->n_groups * kThreads : 0;  // lane-tile form, arm 40
-        // (tuning arms 66 / 67: A_(4 sq) as byte tables for the chains of the
-        // two-tile forms)
-        const size_t n_tbt = (ZHIP_TUNING && (t4w || tgw)) ? (size_t)kByteTabWords : 0;
-        std::vector<uint32_t> ht(n_base + n_t4 + n_g + n_t4f + n_t4w + n_tgw + n_t2w + n_t1w + n_tg2w + n_t2e + n_t2 +
-                                 n_tgl + n_tbt);
-        build_horner_stride(ht.data(), 16ull * sq);
-        for (int t = 0; t < kThreads; ++t) {
-            const uint64_t rel = (uint64_t)(kTileRows + t / 16) * sq + 16u * (t % 16);
-            ht[4096 + t] = xpow8(REF - rel);
-        }
-        for (uint32_t ti = 0; ti < T; ++ti) ht[4096 + kThreads + ti] = xpow8(Rc - base[ti] - REF);
-        p->t_c_inv = xpow8_inv(Rc - L.nbytes);
-        if (t4) {
-            p->tile4_off_tz = n_base;
-            p->tile4_off_kq = n_base + 1024;
-            p->tile4_off_map = n_base + 1024 + (size_t)(T / 4) * kThreads;
-            const uint32_t z = xpow8(step);
-            for (int sl = 0; sl < 4; ++sl)
-                for (uint32_t b = 0; b < 256; ++b) ht[p->tile4_off_tz + sl * 256 + b] = gf_mul(z, b << (8 * sl));
-            for (uint32_t g4 = 0; g4 < T / 4; ++g4) {
-                const uint32_t ku = gf_mul(ht[4096 + kThreads + 4 * g4 + 3], p->t_c_inv);
-                for (int t = 0; t < kThreads; ++t)
-                    ht[p->tile4_off_kq + (size_t)g4 * kThreads + t] = gf_mul(ht[4096 + t], ku);
-            }
-            // out offset of each tile relative to the chunk's out_off (full selection)
-            for (uint32_t ti = 0; ti < T; ++ti) {
-                uint32_t r = ti;
-                const uint32_t cb = r % p->n_cb;
-                r /= p->n_cb;
-                const uint32_t qb = r % p->n_qb;
-                r /= p->n_qb;
-                int64_t o = (int64_t)qb * kTileRows * L.out_stride[p->tq] +
-                            (int64_t)cb * (kTileCols / L.itemsize) * L.out_stride[L.ndim - 1];
-                for (int d = L.ndim - 2; d >= 0; --d) {
-                    if (d == p->tq) continue;
-                    o += (int64_t)(r % (uint32_t)L.shape[d]) * L.out_stride[d];
-                    r /= (uint32_t)L.shape[d];
-                }
-                uint32_t* e = &ht[p->tile4_off_map + 4ull * ti];
-                e[0] = (uint32_t)base[ti];
-                e[1] = 0;
-                std::memcpy(e + 2, &o, sizeof(o));
-            }
-        }
-        if (p->gd >= 0) {
-            // groups: tiles whose gd coordinate is 4m .. 4m+3, others equal
-            p->g_off_tz = n_base + n_t4;
-            p->g_off_map = p->g_off_tz + 1024;
-            const uint32_t z = xpow8(p->sstride[p->gd]);
-            for (int sl = 0; sl < 4; ++sl)
-                for (uint32_t b = 0; b < 256; ++b) ht[p->g_off_tz + sl * 256 + b] = gf_mul(z, b << (8 * sl));
-            // tile-index stride of the gd coordinate (natural order: cb, qb, then
-            // the other dims from ndim-2 down)
-            uint64_t tstride = (uint64_t)p->n_cb * p->n_qb;
-            for (int d = L.ndim - 2; d > p->gd; --d)
-                if (d != p->tq) tstride *= (uint64_t)L.shape[d];
-            GroupEnt* gm = reinterpret_cast<GroupEnt*>(&ht[p->g_off_map]);
-            uint32_t g = 0;
-            for (uint32_t ti = 0; ti < T; ++ti) {
-                if ((ti / tstride) % (uint64_t)L.shape[p->gd] % 4u != 0u) continue;
-                uint32_t r = ti;
-                const uint32_t cb = r % p->n_cb;
-                r /= p->n_cb;
-                const uint32_t qb = r % p->n_qb;
-                r /= p->n_qb;
-                int64_t o = (int64_t)qb * kTileRows * L.out_stride[p->tq] +
-                            (int64_t)cb * (kTileCols / L.itemsize) * L.out_stride[L.ndim - 1];
-                for (int d = L.ndim - 2; d >= 0; --d) {
-                    if (d == p->tq) continue;
-                    o += (int64_t)(r % (uint32_t)L.shape[d]) * L.out_stride[d];
-                    r /= (uint32_t)L.shape[d];
-                }
-                GroupEnt e{};
-                e.tbase = (uint32_t)base[ti];
-                e.rows = (uint16_t)std::min<int64_t>(kTileRows, (int64_t)L.shape[p->tq] - (int64_t)qb * kTileRows);
-                e.cols = (uint16_t)std::min<int64_t>(kTileCols, (int64_t)p->row_bytes - (int64_t)cb * kTileCols);
-                e.orel = o;
-                e.ku = gf_mul(ht[4096 + kThreads + ti + 3 * tstride], p->t_c_inv);
-                gm[g++] = e;
-            }
-        }
-        p->tile4f = t4f ? 1u : 0u;
-        p->tile4f_off = n_base + n_t4 + n_g;
-        if (t4f) {
-            // A_64 in the pair kernel's 11/11/10 layout; the lane constant (the
-            // il kernel's frame, D = 64, 16 blocks) x^(8 (E - p_0 + 4096 - 16 * 64))
-            // c_inv x^(-96) gives every word at p the pair kernel's
-            // x^(8 (E - p + 4096)) c_inv (p_0: the lane's first block)
-            uint32_t* f = &ht[p->tile4f_off];
-            build_pair_tables(f, 64);
-            const uint32_t c96 = xpow8_inv(12);
-            for (uint32_t g4 = 0; g4 < T / 4; ++g4)
-                for (int t = 0; t < kThreads; ++t) {
-                    const int64_t p0 = (int64_t)base[4 * g4] + (int64_t)(t / 4) * (int64_t)sq + 16 * (t % 4);
-                    const int64_t e = (int64_t)p->E - p0 + kWgStride - 16 * 64;
-                    const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                    f[kPairTabWords + (size_t)g4 * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-                }
-        }
-        p->tile4w = t4w ? 1u : 0u;
-        p->tile4w_off = n_base + n_t4 + n_g + n_t4f;
-        if (t4w) {
-            // A_(4 sq); lane constant (the il frame, D = 4 sq, 16 blocks)
-            // x^(8 (E - p_0 + 4096 - 16 D)) c_inv x^(-96), p_0 = base[4 g + w] +
-            // (l / 16) sq + 16 (l % 16) for thread t = 64 w + l
-            uint32_t* f = &ht[p->tile4w_off];
-            const uint64_t D = 4ull * sq;
-            build_pair_tables(f, D);
-            const uint32_t c96 = xpow8_inv(12);
-            for (uint32_t g4 = 0; g4 < T / 4; ++g4)
-                for (int t = 0; t < kThreads; ++t) {
-                    const int w = t / 64, l = t % 64;
-                    const int64_t p0 = (int64_t)base[4 * g4 + w] + (int64_t)(l / 16) * (int64_t)sq + 16 * (l % 16);
-                    const int64_t e = (int64_t)p->E - p0 + kWgStride - 16 * (int64_t)D;
-                    const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                    f[kPairTabWords + (size_t)g4 * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-                }
-        }
-        p->tile2w_off = 0;
-        if (n_t2w) {
-            // two tiles per workgroup: wave w loads rows 32 (w % 2) + l/16 + 4 m (m < 8)
-            // of tile 2 g + w / 2; the same frame with 8 blocks of stride D = 4 sq
-            p->tile2w_off = n_base + n_t4 + n_g + n_t4f + n_t4w + n_tgw;
-            uint32_t* f = &ht[p->tile2w_off];
-            const uint64_t D = 4ull * sq;
-            const uint32_t c96 = xpow8_inv(12);
-            for (uint32_t g2 = 0; g2 < T / 2; ++g2)
-                for (int t = 0; t < kThreads; ++t) {
-                    const int w = t / 64, l = t % 64;
-                    const int64_t p0 = (int64_t)base[2 * g2 + w / 2] + (int64_t)(32 * (w % 2) + l / 16) * (int64_t)sq +
-                                       16 * (l % 16);
-                    const int64_t e = (int64_t)p->E - p0 + kWgStride - 8 * (int64_t)D;
-                    const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                    f[(size_t)g2 * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-                }
-        }
-        p->tile1w_off = 0;
-        if (n_t1w) {
-            // one tile per workgroup: wave w loads rows 16 w + l/16 + 4 m (m < 4)
-            p->tile1w_off = n_base + n_t4 + n_g + n_t4f + n_t4w + n_tgw + n_t2w;
-            uint32_t* f = &ht[p->tile1w_off];
-            const uint64_t D = 4ull * sq;
-            const uint32_t c96 = xpow8_inv(12);
-            for (uint32_t ti = 0; ti < T; ++ti)
-                for (int t = 0; t < kThreads; ++t) {
-                    const int w = t / 64, l = t % 64;
-                    const int64_t p0 = (int64_t)base[ti] + (int64_t)(16 * w + l / 16) * (int64_t)sq + 16 * (l % 16);
-                    const int64_t e = (int64_t)p->E - p0 + kWgStride - 4 * (int64_t)D;
-                    const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                    f[(size_t)ti * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-                }
-        }
-        p->tileg2w_off = 0;
-        if (n_tg2w) {
-            // workgroup 2 g + h of a chunk: tiles 2 h, 2 h + 1 of group g, wave w loading
-            // rows 32 (w % 2) + l/16 + 4 m (m < 8) of tile 2 h + w / 2
-            p->tileg2w_off = n_base + n_t4 + n_g + n_t4f + n_t4w + n_tgw + n_t2w + n_t1w;
-            uint32_t* f = &ht[p->tileg2w_off];
-            const uint64_t D = 4ull * sq;
-            const uint32_t c96 = xpow8_inv(12);
-            const GroupEnt* gm = reinterpret_cast<const GroupEnt*>(&ht[p->g_off_map]);
-            const int64_t gstep = (int64_t)p->sstride[p->gd];
-            for (uint32_t g = 0; g < p->n_groups; ++g)
-                for (uint32_t h = 0; h < 2; ++h)
-                    for (int t = 0; t < kThreads; ++t) {
-                        const int w = t / 64, l = t % 64;
-                        const int64_t p0 = (int64_t)gm[g].tbase + (int64_t)(2 * h + w / 2) * gstep +
-                                           (int64_t)(32 * (w % 2) + l / 16) * (int64_t)sq + 16 * (l % 16);
-                        const int64_t e = (int64_t)p->E - p0 + kWgStride - 8 * (int64_t)D;
-                        const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                        f[((size_t)g * 2 + h) * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-                    }
-        }
-        p->tile2e_off = 0;
-        if (n_t2e) {
-            // the four-tile constants' form for groups of two: the state carried
-            // to the group's last tile (tile 2 g + 1), then shifted by its unit constant
-            p->tile2e_off = n_base + n_t4 + n_g + n_t4f + n_t4w + n_tgw + n_t2w + n_t1w + n_tg2w;
-            for (uint32_t g2 = 0; g2 < T / 2; ++g2) {
-                const uint32_t ku = gf_mul(ht[4096 + kThreads + 2 * g2 + 1], p->t_c_inv);
-                for (int t = 0; t < kThreads; ++t)
-                    ht[p->tile2e_off + (size_t)g2 * kThreads + t] = gf_mul(ht[4096 + t], ku);
-            }
-        }
-        p->tile2_off = 0;
-        if (n_t2) {
-            p->tile2_off = n_base + n_t4 + n_g + n_t4f + n_t4w + n_tgw + n_t2w + n_t1w + n_tg2w + n_t2e;
-            uint32_t* f = &ht[p->tile2_off];
-            const uint64_t D = 4ull * sq;
-            build_pair_tables(f, D);
-            // tile map (as tile4's): stored base, out offset relative to the chunk's out_off
-            for (uint32_t ti = 0; ti < T; ++ti) {
-                uint32_t r = ti;
-                const uint32_t cb = r % p->n_cb;
-                r /= p->n_cb;
-                const uint32_t qb = r % p->n_qb;
-                r /= p->n_qb;
-                int64_t o = (int64_t)qb * kTileRows * L.out_stride[p->tq] +
-                            (int64_t)cb * (kTileCols / L.itemsize) * L.out_stride[L.ndim - 1];
-                for (int d = L.ndim - 2; d >= 0; --d) {
-                    if (d == p->tq) continue;
-                    o += (int64_t)(r % (uint32_t)L.shape[d]) * L.out_stride[d];
-                    r /= (uint32_t)L.shape[d];
-                }
-                uint32_t* e = &f[kPairTabWords + 4ull * ti];
-                e[0] = (uint32_t)base[ti];
-                e[1] = 0;
-                std::memcpy(e + 2, &o, sizeof(o));
-            }
-            // lane constants: wave w of pair g loads rows 32 (w % 2) + l/16 + 4 m (m < 8) of tile 2 g + w / 2
-            const uint32_t c96 = xpow8_inv(12);
-            uint32_t* kc = f + kPairTabWords + (size_t)T * 4;
-            for (uint32_t g2 = 0; g2 < T / 2; ++g2)
-                for (int t = 0; t < kThreads; ++t) {
-                    const int w = t / 64, l = t % 64;
-                    const int64_t p0 = (int64_t)base[2 * g2 + w / 2] + (int64_t)(32 * (w % 2) + l / 16) * (int64_t)sq +
-                                       16 * (l % 16);
-                    const int64_t e = (int64_t)p->E - p0 + kWgStride - 8 * (int64_t)D;
-                    const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                    kc[(size_t)g2 * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-                }
-        }
-        p->tilegl_off = 0;
-        if (n_tgl) {
-            // lane l of wave w: rows w + 4 m (m < 16) of tile l / 16 at column block l % 16
-            p->tilegl_off = n_base + n_t4 + n_g + n_t4f + n_t4w + n_tgw + n_t2w + n_t1w + n_tg2w + n_t2e + n_t2;
-            uint32_t* f = &ht[p->tilegl_off];
-            const uint64_t D = 4ull * sq;
-            const uint32_t c96 = xpow8_inv(12);
-            const GroupEnt* gm = reinterpret_cast<const GroupEnt*>(&ht[p->g_off_map]);
-            const int64_t gstep = (int64_t)p->sstride[p->gd];
-            for (uint32_t g = 0; g < p->n_groups; ++g)
-                for (int t = 0; t < kThreads; ++t) {
-                    const int w = t / 64, l = t % 64;
-                    const int64_t p0 = (int64_t)gm[g].tbase + (int64_t)(l / 16) * gstep + (int64_t)w * (int64_t)sq +
-                                       16 * (l % 16);
-                    const int64_t e = (int64_t)p->E - p0 + kWgStride - 16 * (int64_t)D;
-                    const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                    f[(size_t)g * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-                }
-        }
-        p->tilebt_off = 0;
-        if (n_tbt) {
-            p->tilebt_off = n_base + n_t4 + n_g + n_t4f + n_t4w + n_tgw + n_t2w + n_t1w + n_tg2w + n_t2e + n_t2 + n_tgl;
-            uint32_t* f = &ht[p->tilebt_off];
-            const uint32_t x = xpow8(4ull * sq), x4 = xpow8(4);
-            for (int sl = 0; sl < 4; ++sl)
-                for (uint32_t b = 0; b < 256; ++b) {
-                    f[sl * 256 + b] = gf_mul(x, b << (8 * sl));
-                    f[1024 + sl * 256 + b] = gf_mul(x4, b << (8 * sl));
-                }
-        }
-        p->tilegw = tgw ? 1u : 0u;
-        p->tilegw_off = n_base + n_t4 + n_g + n_t4f + n_t4w;
-        if (tgw) {
-            // as k_decode_tile4w, tile w of group g at gm[g].tbase + w step(gd)
-            uint32_t* f = &ht[p->tilegw_off];
-            const uint64_t D = 4ull * sq;
-            build_pair_tables(f, D);
-            const uint32_t c96 = xpow8_inv(12);
-            const GroupEnt* gm = reinterpret_cast<const GroupEnt*>(&ht[p->g_off_map]);
-            const int64_t gstep = (int64_t)p->sstride[p->gd];
-            for (uint32_t g = 0; g < p->n_groups; ++g)
-                for (int t = 0; t < kThreads; ++t) {
-                    const int w = t / 64, l = t % 64;
-                    const int64_t p0 = (int64_t)gm[g].tbase + w * gstep + (int64_t)(l / 16) * (int64_t)sq +
-                                       16 * (l % 16);
-                    const int64_t e = (int64_t)p->E - p0 + kWgStride - 16 * (int64_t)D;
-                    const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-                    f[kPairTabWords + (size_t)g * kThreads + t] = gf_mul(gf_mul(xe, p->c_inv), c96);
-                }
-        }
+        const std::vector<uint32_t> ht = build_tile_tables(*p);
         if (p->d_tile_tables) (void)hipFree(p->d_tile_tables);
         p->d_tile_tables = nullptr;
         HIP_TRY(hipMalloc(&p->d_tile_tables, ht.size() * sizeof(uint32_t)));
@@ -876,15 +285,15 @@ int zhip_plan_info(const zhip_plan* p, uint32_t* units_per_chunk, uint32_t* work
     // + the grouped kernels' / k_decode_xw's arrival subwords
     // (CRC layouts: >= kPubLine, the il / tile4 publication lines)
     // (k_decode_tilegw's two-tile form: arrival subwords for twice the groups)
-    // (known at plan creation, before the tile tables exist)
-    const bool tg2w = p->gd >= 0 && (p->layout.flags & ZHIP_LF_CRC);
+    const TableLayout& T = p->tl;
+    const bool tg2w = T.tg2w.n != 0;
     uint32_t n_sub2 = (tg2w && 2 * p->n_groups > 16u && 2 * p->n_groups <= 256u)
                           ? (2 * p->n_groups + 15u) / 16u : 0u;
     // (the tile-pair decode, tuning builds: subwords of 16 for 33..256 workgroups per chunk)
-    const uint32_t wpc2 = (ZHIP_TUNING && p->tile2) ? p->t_per_chunk / 2u : 0u;
+    const uint32_t wpc2 = T.tile2_tab.n ? p->t_per_chunk / 2u : 0u;
     if (wpc2 > 32u && wpc2 <= 256u) n_sub2 = std::max(n_sub2, (wpc2 + 15u) / 16u);
     // (k_decode_tile4w, four tiles per workgroup: the same subwords past 32 workgroups per chunk)
-    const uint32_t wpc4 = (p->tile4 && (p->layout.flags & ZHIP_LF_CRC)) ? p->t_per_chunk / 4u : 0u;
+    const uint32_t wpc4 = T.t4w.tab.n ? p->t_per_chunk / 4u : 0u;
     if (wpc4 > 32u && wpc4 <= 256u) n_sub2 = std::max(n_sub2, (wpc4 + 15u) / 16u);
     uint32_t w = std::max(4 + 2 * std::max(std::max(p->n_sub, p->xw_nsub), n_sub2),
                           (p->layout.flags & ZHIP_LF_CRC) ? kPubLine : 0u);
@@ -1054,6 +463,27 @@ int zhip_rows_map(const zhip_plan* plan, const zhip_sel* h_sels, uint32_t n_sels
 // (zhip_decode_mapped launches them, zhip_decode_mapped_multi several in one
 // grid).  `empty`: nothing to decode, p is not filled.
 extern "C++" {
+// Device pointers of the plan's regions (plan->tl); null where a region is absent.
+static const uint32_t* row_at(const zhip_plan* plan, const Region& r) { return r.n ? plan->d_tables + r.off : nullptr; }
+static const uint32_t* tile_at(const zhip_plan* plan, const Region& r) {
+    return r.n ? plan->d_tile_tables + r.off : nullptr;
+}
+template <class T>
+static const T* tile_at(const zhip_plan* plan, const Region& r) {
+    return reinterpret_cast<const T*>(tile_at(plan, r));
+}
+
+// k_decode_il / k_encode_il's table set: il_choose's interleave and its four pointers
+struct IlTables {
+    uint32_t S;
+    const uint32_t *tab, *klane, *kidx, *basis;
+};
+static IlTables il_tables(const zhip_plan* plan, uint32_t want) {
+    const IlChoice c = il_choose(*plan, want);
+    return {c.S, row_at(plan, c.set->tab), row_at(plan, c.set->klane), row_at(plan, c.set->kidx),
+            row_at(plan, c.set->basis)};
+}
+
 static int mapped_params(const zhip_plan* plan, const void* src, uint64_t src_size, void* out,
                          const zhip_chunk* d_chunks, uint32_t n_chunks, const zhip_sel* d_sels,
                          zhip_status* d_status, uint32_t* d_workspace, uint32_t* d_errflag,
@@ -1093,41 +523,32 @@ static int mapped_params(const zhip_plan* plan, const void* src, uint64_t src_si
     p.status = d_status;
     p.ws = d_workspace;
     p.errflag = d_errflag;
-    p.horner = plan->d_tables;
-    p.kthread = plan->d_tables + 4096;
-    p.kunit = plan->d_tables + 4096 + kThreads;
-    p.kpair = plan->d_tables + 4096 + kThreads + plan->nseg;
-    p.pair_tab = plan->d_tables + plan->off_pair;
-    p.kpair11 = p.pair_tab + kPairTabWords;
-    p.kthread11 = p.kpair11 + (size_t)plan->nseg * kThreads;
+    const TableLayout& T = plan->tl;
+    p.horner = row_at(plan, T.horner);
+    p.kthread = row_at(plan, T.kthread);
+    p.kunit = row_at(plan, T.kunit);
+    p.kpair = row_at(plan, T.kpair);
+    p.pair_tab = row_at(plan, T.pair.tab);
+    p.kpair11 = row_at(plan, T.pair.klane);
+    p.kthread11 = row_at(plan, T.pair.kidx);
     // k_decode_il needs its tables, and a fused index check of one step per lane
-    p.il_S = (plan->il_S && (n_index == 0 || plan->idx_E <= (uint32_t)kWgStride)) ? plan->il_S : 0u;
-    // the widest interleave the plan built (S = 32, else 16, else 8); tuning
-    // arms 69 / 70 / 71 force 16 / 32 / 8
-    int si = plan->off_il_s[1] ? 1 : plan->off_il_s[0] ? 0 : -1;
-#if ZHIP_TUNING
-    if (g_tune_arm == kArmIlS16) si = plan->off_il_s[0] ? 0 : -1;
-    if (g_tune_arm == kArmIlS32) si = plan->off_il_s[1] ? 1 : -1;
-    if (g_tune_arm == kArmIlS8) si = -1;
-#endif
-    if (p.il_S && si >= 0) {  // groups of 16 / 32 workgroups: the plan's second / third table set
-        p.il_S = 16u << si;
-        p.il_tab = plan->d_tables + plan->off_il_s[si];
-        p.il_klane = p.il_tab + kPairTabWords;
-        p.il_kidx = p.il_klane + (size_t)plan->nseg * kThreads;
-        p.il_basis = p.il_kidx + kThreads;
-    } else if (p.il_S) {
-        p.il_tab = plan->d_tables + plan->off_il;
-        p.il_klane = p.il_tab + kPairTabWords;
-        p.il_kidx = p.il_klane + (size_t)plan->nseg * kThreads;
-        p.il_basis = p.il_kidx + kThreads;
+    if (plan->il_S && (n_index == 0 || plan->idx_E <= (uint32_t)kWgStride)) {
+        // the widest interleave the plan built (S = 32, else 16, else 8); tuning
+        // arms 69 / 70 / 71 force 16 / 32 / 8
+        const IlTables il = il_tables(plan, g_tune_arm == kArmIlS16 ? 16u : g_tune_arm == kArmIlS32 ? 32u
+                                            : g_tune_arm == kArmIlS8 ? 8u : 0u);
+        p.il_S = il.S;
+        p.il_tab = il.tab;
+        p.il_klane = il.klane;
+        p.il_kidx = il.kidx;
+        p.il_basis = il.basis;
     }
     p.xw = (plan->xw_P && (n_index == 0 || plan->idx_E <= (uint32_t)kWgStride)) ? plan->xw_P : 0u;
     if (p.xw) {
         p.xw_nsub = plan->xw_nsub;
-        p.xw_tab = plan->d_tables + plan->off_xw;
-        p.xw_klane = p.xw_tab + kPairTabWords;
-        p.xw_kidx = p.xw_klane + (size_t)plan->xw_P * 64;
+        p.xw_tab = row_at(plan, T.xw.tab);
+        p.xw_klane = row_at(plan, T.xw.klane);
+        p.xw_kidx = row_at(plan, T.xw.kidx);
     }
     // k_decode_ilw: 512 lanes per unit for grids of at most kIlwMaxUnits
     // units (launch_decode; tuning arms 26 / 31 force 1024 lanes, 27 / 32 512)
@@ -1140,14 +561,14 @@ static int mapped_params(const zhip_plan* plan, const void* src, uint64_t src_si
         if ((arm_in(kArmIlw1024, kArmIlw512Reg) || g_tune_arm == kArmIlw512Half) &&
             !(n_index == 0 || plan->idx_E <= (uint32_t)kWgStride)) wi = -1;
 #endif
-        p.ilw_nt = (wi >= 0 && plan->off_ilw[wi]) ? (1024u >> wi) : 0u;
+        p.ilw_nt = (wi >= 0 && T.ilw[wi].tab.n) ? (1024u >> wi) : 0u;
         if (p.ilw_nt) {
-            p.ilw_tab = plan->d_tables + plan->off_ilw[wi];
-            p.ilw_klane = p.ilw_tab + kPairTabWords;
-            p.ilw_kidx = p.ilw_klane + (size_t)plan->nseg * p.ilw_nt;
+            p.ilw_tab = row_at(plan, T.ilw[wi].tab);
+            p.ilw_klane = row_at(plan, T.ilw[wi].klane);
+            p.ilw_kidx = row_at(plan, T.ilw[wi].kidx);
         }
     }
-    if (plan->off_ilh) p.ilh_klane = plan->d_tables + plan->off_ilh;
+    p.ilh_klane = row_at(plan, T.ilh);
     // whole-chunk selections (ZHIP_DF_WHOLE, with a row map) of a plan whose
     // whole-chunk row map is affine: the row kernels compute destinations
     // (tuning arm 45 keeps the map loads: the A/B reference)
@@ -1224,52 +645,52 @@ static int mapped_params(const zhip_plan* plan, const void* src, uint64_t src_si
         for (int d = 0; d < ZHIP_MAX_DIMS; ++d) p.sstride[d] = plan->sstride[d];
         p.d_qb = make_fdiv(plan->n_qb);
         p.d_cb = make_fdiv(plan->n_cb);
-        p.horner = plan->d_tile_tables;
-        p.kthread = plan->d_tile_tables + 4096;
-        p.kunit = plan->d_tile_tables + 4096 + kThreads;
+        p.horner = tile_at(plan, T.t_horner);
+        p.kthread = tile_at(plan, T.t_kthread);
+        p.kunit = tile_at(plan, T.t_kunit);
         p.c_inv = plan->t_c_inv;
         p.tile4 = plan->tile4 && !(g_tune_bits & (kTuneTile1 | kTuneNoTile4));
         if (p.tile4) {
-            p.tz = plan->d_tile_tables + plan->tile4_off_tz;
-            p.kq4 = plan->d_tile_tables + plan->tile4_off_kq;
-            p.tmap = reinterpret_cast<const TileEnt*>(plan->d_tile_tables + plan->tile4_off_map);
+            p.tz = tile_at(plan, T.tile4_tz);
+            p.kq4 = tile_at(plan, T.tile4_kq);
+            p.tmap = tile_at<TileEnt>(plan, T.tile4_map);
             if (plan->tile4f && (g_tune_bits & kTuneTile4F)) {  // arm: measured 0.3-0.4 us slower on C3
-                p.t4f_tab = plan->d_tile_tables + plan->tile4f_off;
-                p.t4f_kq = p.t4f_tab + kPairTabWords;
+                p.t4f_tab = tile_at(plan, T.t4f.tab);
+                p.t4f_kq = tile_at(plan, T.t4f.klane);
             } else if (plan->tile4w && g_tune_arm != kArmPub16 && g_tune_arm != kArmDeferred &&
                        g_tune_arm != kArmNoWaveTile) {
                 // production for CRC layouts: a wave per tile, one chain per lane (k_decode_tile4w:
                 // C3 28.9 vs 30.3-30.6 us, profiles/r04/k); arms 1 / 2 / 5: k_decode_tile4
-                p.t4w_tab = plan->d_tile_tables + plan->tile4w_off;
-                p.t4w_kq = p.t4w_tab + kPairTabWords;
-                if (plan->tilebt_off) p.tbt_tab = plan->d_tile_tables + plan->tilebt_off;
-                if (plan->tile2w_off) p.t2w_kq = plan->d_tile_tables + plan->tile2w_off;
-                if (plan->tile1w_off) p.t1w_kq = plan->d_tile_tables + plan->tile1w_off;
+                p.t4w_tab = tile_at(plan, T.t4w.tab);
+                p.t4w_kq = tile_at(plan, T.t4w.klane);
+                p.tbt_tab = tile_at(plan, T.tbt_ad);
+                p.t2w_kq = tile_at(plan, T.t2w);
+                p.t1w_kq = tile_at(plan, T.t1w);
             }
-        } else if (plan->tile2 && plan->tile2_off && !(g_tune_bits & kTuneTile1) && g_tune_arm == kArmTilePairs) {
+        } else if (plan->tile2 && T.tile2_tab.n && !(g_tune_bits & kTuneTile1) && g_tune_arm == kArmTilePairs) {
             // consecutive tile pairs (k_decode_tile4w<2>) where tile4 declines
             // (tuning arm 39; the grouped kernels are faster)
             p.tile2 = 1;
-            p.t4w_tab = plan->d_tile_tables + plan->tile2_off;
-            p.tmap = reinterpret_cast<const TileEnt*>(p.t4w_tab + kPairTabWords);
-            p.t4w_kq = p.t4w_tab + kPairTabWords + (size_t)plan->t_per_chunk * 4;
+            p.t4w_tab = tile_at(plan, T.tile2_tab);
+            p.tmap = tile_at<TileEnt>(plan, T.tile2_map);
+            p.t4w_kq = tile_at(plan, T.tile2_klane);
         } else if (plan->gd >= 0 && !(g_tune_bits & kTuneTile1) &&
                    L.shape[plan->tq] % (16 / L.itemsize) == 0) {
             // k_decode_tileg: tiles grouped by four along gd, whole out pieces
             p.tileg = 1;
-            p.gtz = plan->d_tile_tables + plan->g_off_tz;
-            p.gmap = reinterpret_cast<const GroupEnt*>(plan->d_tile_tables + plan->g_off_map);
+            p.gtz = tile_at(plan, T.g_tz);
+            p.gmap = tile_at<GroupEnt>(plan, T.g_map);
             p.n_groups = plan->n_groups;
             p.n_sub = plan->n_sub;
             p.g_step_t = plan->sstride[plan->gd];
             p.g_step_o = L.out_stride[plan->gd];
             // a wave per tile, one chain per lane
             if (plan->tilegw && g_tune_arm != kArmDeferred && g_tune_arm != kArmNoWaveTile) {
-                p.t4w_tab = plan->d_tile_tables + plan->tilegw_off;
-                p.t4w_kq = p.t4w_tab + kPairTabWords;
-                if (plan->tileg2w_off) p.t2w_kq = plan->d_tile_tables + plan->tileg2w_off;  // two tiles per workgroup
-                if (plan->tilegl_off) p.tglt_kq = plan->d_tile_tables + plan->tilegl_off;    // (arm 40)
-                if (plan->tilebt_off) p.tbt_tab = plan->d_tile_tables + plan->tilebt_off;    // (arm 66)
+                p.t4w_tab = tile_at(plan, T.tgw.tab);
+                p.t4w_kq = tile_at(plan, T.tgw.klane);
+                p.t2w_kq = tile_at(plan, T.tg2w);  // two tiles per workgroup
+                p.tglt_kq = tile_at(plan, T.tgl);  // (arm 40)
+                p.tbt_tab = tile_at(plan, T.tbt_ad);  // (arm 66)
             }
         }
         const uint64_t tunits = (uint64_t)n_chunks * plan->t_per_chunk;
@@ -1369,9 +790,10 @@ int zhip_encode_mapped(const zhip_plan* plan, const void* arr, void* dst, const 
     p.status = d_status;
     p.ws = d_workspace;
     p.nonempty = d_nonempty;
-    p.horner = plan->d_tables;
-    p.kthread = plan->d_tables + 4096;
-    p.kunit = plan->d_tables + 4096 + kThreads;
+    const TableLayout& T = plan->tl;
+    p.horner = row_at(plan, T.horner);
+    p.kthread = row_at(plan, T.kthread);
+    p.kunit = row_at(plan, T.kunit);
     p.n_chunks = n_chunks;
     p.nseg = plan->nseg;
     p.n_units = (uint32_t)units;
@@ -1401,11 +823,11 @@ int zhip_encode_mapped(const zhip_plan* plan, const void* arr, void* dst, const 
         p.tq = plan->tq;
         p.t_per_chunk = plan->t_per_chunk;
         for (int d = 0; d < ZHIP_MAX_DIMS; ++d) p.sstride[d] = plan->sstride[d];
-        p.horner = plan->d_tile_tables;
-        p.tz = plan->d_tile_tables + plan->tile4_off_tz;
-        p.kq4 = plan->d_tile_tables + plan->tile4_off_kq;
-        if (plan->tile2e_off) p.kq2 = plan->d_tile_tables + plan->tile2e_off;
-        p.tmap = reinterpret_cast<const TileEnt*>(plan->d_tile_tables + plan->tile4_off_map);
+        p.horner = tile_at(plan, T.t_horner);
+        p.tz = tile_at(plan, T.tile4_tz);
+        p.kq4 = tile_at(plan, T.tile4_kq);
+        p.kq2 = tile_at(plan, T.t2e);
+        p.tmap = tile_at<TileEnt>(plan, T.tile4_map);
         d_rowmap = nullptr;
     } else if ((encode_flags & ZHIP_DF_TILE) && plan->gd >= 0 && plan->d_tile_tables && !(g_tune_bits & kTuneTile1) &&
                L.shape[plan->tq] % (16 / L.itemsize) == 0 && plan->n_groups < 65536u) {
@@ -1415,16 +837,16 @@ int zhip_encode_mapped(const zhip_plan* plan, const void* arr, void* dst, const 
         p.tq = plan->tq;
         p.t_per_chunk = plan->t_per_chunk;
         for (int d = 0; d < ZHIP_MAX_DIMS; ++d) p.sstride[d] = plan->sstride[d];
-        p.horner = plan->d_tile_tables;
-        p.kthread = plan->d_tile_tables + 4096;
-        p.gtz = plan->d_tile_tables + plan->g_off_tz;
-        p.gmap = reinterpret_cast<const GroupEnt*>(plan->d_tile_tables + plan->g_off_map);
+        p.horner = tile_at(plan, T.t_horner);
+        p.kthread = tile_at(plan, T.t_kthread);
+        p.gtz = tile_at(plan, T.g_tz);
+        p.gmap = tile_at<GroupEnt>(plan, T.g_map);
         p.n_groups = plan->n_groups;
         p.n_sub = plan->n_sub;
         p.g_step_t = plan->sstride[plan->gd];
         p.g_z2 = xpow8(2ull * plan->sstride[plan->gd]);
         p.g_step_o = L.out_stride[plan->gd];
-        if (plan->tilebt_off) p.g_a4 = plan->d_tile_tables + plan->tilebt_off + 1024;  // (arm 68)
+        p.g_a4 = tile_at(plan, T.tbt_a4);  // (arm 68)
         p.g_c96 = xpow8_inv(12);
         d_rowmap = nullptr;
     } else if ((encode_flags & (ZHIP_DF_TILE | ZHIP_DF_TILE_PREFIX)) && plan->tq >= 0 && plan->d_tile_tables &&
@@ -1439,9 +861,9 @@ int zhip_encode_mapped(const zhip_plan* plan, const void* arr, void* dst, const 
         p.d_qb = make_fdiv(plan->n_qb);
         p.d_cb = make_fdiv(plan->n_cb);
         for (int d = 0; d < ZHIP_MAX_DIMS; ++d) p.sstride[d] = plan->sstride[d];
-        p.horner = plan->d_tile_tables;
-        p.kthread = plan->d_tile_tables + 4096;
-        p.kunit = plan->d_tile_tables + 4096 + kThreads;
+        p.horner = tile_at(plan, T.t_horner);
+        p.kthread = tile_at(plan, T.t_kthread);
+        p.kunit = tile_at(plan, T.t_kunit);
         p.c_inv = plan->t_c_inv;
         d_rowmap = nullptr;
     }
@@ -1452,19 +874,18 @@ int zhip_encode_mapped(const zhip_plan* plan, const void* arr, void* dst, const 
             (uint32_t)L.shape[nd - 2] % ((uint32_t)kWgStride / rb) != 0)
             return set_err(ZHIP_E_INVALID, "row map given for a layout without whole-row encode");
         p.rowmap = d_rowmap;
-        p.kpair = plan->d_tables + 4096 + kThreads + plan->nseg;
-        p.pair_tab = plan->d_tables + plan->off_pair;
-        p.kpair11 = p.pair_tab + kPairTabWords;
+        p.kpair = row_at(plan, T.kpair);
+        p.pair_tab = row_at(plan, T.pair.tab);
+        p.kpair11 = row_at(plan, T.pair.klane);
         p.row_shift = (uint32_t)__builtin_ctz(rb);
         p.r_oy = L.out_stride[nd - 2];
         if (plan->il_S == 8u && (L.flags & ZHIP_LF_CRC)) {  // k_encode_il (launch_encode)
             // the decode's widest interleave (S = 32 / 16 where the steps tile
             // it; tuning arm 73 keeps S = 8)
-            int si = plan->off_il_s[1] ? 1 : plan->off_il_s[0] ? 0 : -1;
-            if (ZHIP_TUNING && g_tune_arm == kArmEncIlS8) si = -1;
-            p.il_S = si >= 0 ? 16u << si : plan->il_S;
-            p.il_tab = plan->d_tables + (si >= 0 ? plan->off_il_s[si] : plan->off_il);
-            p.il_klane = p.il_tab + kPairTabWords;
+            const IlTables il = il_tables(plan, g_tune_arm == kArmEncIlS8 ? 8u : 0u);
+            p.il_S = il.S;
+            p.il_tab = il.tab;
+            p.il_klane = il.klane;
             // whole-chunk selections: destinations computed (ZHIP_DF_WHOLE, as the
             // decode) only in tuning arm 46 -- graph-timed 29.1 vs 28.6 us on the
             // C2 encode (profiles/r05/x/): the encode keeps the row map
@@ -1482,7 +903,6 @@ int zhip_shard_pack(const zhip_plan* plan, void* dst, const zhip_shard* d_shards
                     uint32_t n_inner, uint32_t elen, uint32_t index_size, uint32_t pack_flags,
                     const uint32_t* d_nonempty, uint32_t* d_newrank, const uint32_t* d_rank_of_slot,
                     uint64_t* d_blob_len, void* stream) {
-    std::call_once(g_once, init_tables);
     if (!plan || !plan->d_tables) return set_err(ZHIP_E_INVALID, "plan not uploaded");
     if (n_shards == 0) return ZHIP_OK;
     if (!dst || !d_shards || !d_nonempty || !d_newrank || !d_rank_of_slot || !d_blob_len)
@@ -1495,8 +915,8 @@ int zhip_shard_pack(const zhip_plan* plan, void* dst, const zhip_shard* d_shards
     p.newrank = d_newrank;
     p.rank_of_slot = d_rank_of_slot;
     p.blob_len = d_blob_len;
-    p.horner = plan->d_tables;
-    p.kthread = plan->d_tables + 4096;
+    p.horner = row_at(plan, plan->tl.horner);
+    p.kthread = row_at(plan, plan->tl.kthread);
     p.n_inner = n_inner;
     p.elen = elen;
     p.index_size = index_size;
@@ -1677,66 +1097,99 @@ int zhip_emulate_points(const zhip_points_geom* geom, const int64_t* const* coor
     return ZHIP_OK;
 }
 
-// CPU emulation of the device CRC combine for one chunk of a plan (the exact
-// decomposition, tables and constants the kernel uses).  Test hook: lets the
-// CPU suite prove the algebra without a GPU.
 uint32_t zhip_crc32c_host(const void* data, uint64_t nbytes) {
-    std::call_once(g_once, init_tables);
     const uint8_t* p = static_cast<const uint8_t*>(data);
     if (!nbytes) return 0u;
     static const bool hw = __builtin_cpu_supports("sse4.2");
     return hw ? crc_sse42(p, nbytes) : crc_bytewise(p, nbytes);
 }
 
+// ---- test hooks: the table images, and the kernels' CRC decompositions run on them ----
+uint64_t zhip_plan_table_image(const zhip_plan* plan, int which, uint32_t* out, uint64_t cap) {
+    if (!plan || which < 0 || which > 1 || (which == 1 && plan->tq < 0)) return 0;
+    const std::vector<uint32_t> h = which ? build_tile_tables(*plan) : build_row_tables(*plan);
+    if (out) std::memcpy(out, h.data(), std::min<uint64_t>(cap, h.size()) * sizeof(uint32_t));
+    return h.size();
+}
+
+uint32_t zhip_plan_table_offsets(const zhip_plan* plan, uint64_t* out, uint32_t cap) {
+    if (!plan) return 0;
+    const Region* r = regions(plan->tl);
+    for (uint32_t i = 0; i < kNumRegions && out; ++i) {
+        if (i < cap) out[i] = r[i].off;
+        if (kNumRegions + i < cap) out[kNumRegions + i] = r[i].n;
+    }
+    return kNumRegions;
+}
+
+extern "C++" {
+// the chunk's 16 bytes at offset o as four words, zero outside the payload
+static void load_block(const zhip_plan* plan, const uint8_t* data, int64_t o, uint32_t w[4]) {
+    uint8_t b[16] = {0};
+    for (int i = 0; i < 16; ++i) {
+        const int64_t q = o + i;
+        if (q >= 0 && q < (int64_t)plan->layout.nbytes) b[i] = data[q];
+    }
+    std::memcpy(w, b, 16);
+}
+
+static uint32_t bytes4(const uint32_t* tb, uint32_t x) {  // a [4][256] byte-slice table applied to x
+    return tb[x & 255u] ^ tb[256 + ((x >> 8) & 255u)] ^ tb[512 + ((x >> 16) & 255u)] ^ tb[768 + (x >> 24)];
+}
+
+// The row kernels' four-accumulator scheme on the uploaded tables: lane i (of
+// the klane region's n_lanes) runs its nblk blocks at off(i, k) through the
+// 11/11/10 tables `tab`, folds the four word accumulators with the A4 tables
+// and multiplies by its lane constant klane[i] (mul); lanes xor-combine.  The
+// block schedule off is the kernel's.
+template <class Off, class Mul>
+static uint32_t emulate_lanes(const zhip_plan* plan, const uint8_t* data, const uint32_t* tab, const uint32_t* klane,
+                              uint64_t n_lanes, uint32_t nblk, Off off, Mul mul) {
+    auto a11 = [&](uint32_t w) {
+        return tab[kPairT1 + (w & 2047u)] ^ tab[kPairT2 + ((w >> 11) & 2047u)] ^ tab[kPairT3 + (w >> 22)];
+    };
+    uint32_t V = 0;
+    for (uint64_t i = 0; i < n_lanes; ++i) {
+        uint32_t a[4] = {0, 0, 0, 0}, w[4];
+        for (uint32_t k = 0; k < nblk; ++k) {
+            load_block(plan, data, off((int64_t)i, (int64_t)k), w);
+            for (int j = 0; j < 4; ++j) a[j] = a11(a[j] ^ w[j]);
+        }
+        const uint32_t* t4 = tab + kPairA4;
+        V ^= mul(bytes4(t4, bytes4(t4, bytes4(t4, a[0]) ^ a[1]) ^ a[2]) ^ a[3], klane[i]);
+    }
+    return ~(V ^ plan->c3);
+}
+}
+
+// CPU emulation of the device CRC combine for one chunk of a plan (the exact
+// decomposition, and the tables and constants zhip_plan_upload puts on the
+// device).  Test hook: lets the CPU suite prove the algebra without a GPU.
 uint32_t zhip_emulate_chunk_crc(const zhip_plan* plan, const uint8_t* data) {
-    std::call_once(g_once, init_tables);
-    std::vector<uint32_t> tab(4096);
-    build_horner(tab.data());
-    const uint32_t N = (uint32_t)plan->layout.nbytes;
+    const std::vector<uint32_t> h = build_row_tables(*plan);
+    const TableLayout& T = plan->tl;
     uint32_t V = 0;
     for (uint32_t s = 0; s < plan->nseg; ++s) {
-        const int32_t hi = (int32_t)plan->E - (int32_t)(s * plan->seg);
-        const int32_t lo = hi - (int32_t)plan->seg;
+        const int64_t lo = (int64_t)plan->E - (int64_t)(s + 1) * plan->seg;
         uint32_t unit = 0;
         for (int t = 0; t < kThreads; ++t) {
-            uint32_t acc = 0;
+            uint32_t acc = 0, w[4];
             for (int k = 0; k < (int)plan->kblocks; ++k) {
-                const int32_t o = lo + kWgStride * k + 16 * t;
-                uint8_t b[16] = {0};
-                for (int i = 0; i < 16; ++i) {
-                    const int64_t q = (int64_t)o + i;
-                    if (q >= 0 && q < (int64_t)N) b[i] = data[q];
-                }
-                uint32_t w[4];
-                std::memcpy(w, b, 16);
-                auto ap = [&](int op, uint32_t x) {
-                    const uint32_t* tb = tab.data() + op * 1024;
-                    return tb[x & 255u] ^ tb[256 + ((x >> 8) & 255u)] ^ tb[512 + ((x >> 16) & 255u)] ^
-                           tb[768 + (x >> 24)];
-                };
+                load_block(plan, data, lo + kWgStride * k + 16 * t, w);
+                auto ap = [&](int op, uint32_t x) { return bytes4(&h[T.horner.off + op * 1024], x); };
                 acc = ap(0, acc ^ w[0]) ^ ap(1, w[1]) ^ ap(2, w[2]) ^ ap(3, w[3]);
             }
-            unit ^= gf_mul(acc, xpow8((uint64_t)kWgStride - 16u * t));
+            unit ^= gf_mul(acc, h[T.kthread.off + t]);
         }
-        V ^= gf_mul(unit, xpow8((uint64_t)s * plan->seg));
+        V ^= gf_mul(unit, h[T.kunit.off + s]);
     }
     return ~(gf_mul(V, plan->c_inv) ^ plan->c3);
 }
 
-// CPU emulation of k_decode_pair's CRC for one chunk: 11/11/10-bit A4096
-// tables, four word accumulators per lane folded with the A4 tables, the
-// windowed per-lane multiply by kpair11 (3-bit windows + a 2-bit top window,
-// as the kernel's LDS tables), unit contributions xor-combined.  Test hook.
+// k_decode_pair's scheme: unit s, lane t takes the blocks at 4096 k + 16 t of
+// the unit; the windowed per-lane multiply by kpair11 (3-bit windows + a
+// 2-bit top window, as the kernel's LDS tables).  Test hook.
 uint32_t zhip_emulate_chunk_crc_pair(const zhip_plan* plan, const uint8_t* data) {
-    std::call_once(g_once, init_tables);
-    std::vector<uint32_t> tab(kPairTabWords);
-    build_pair_tables(tab.data());
-    const uint32_t* T = tab.data();
-    auto a11 = [&](uint32_t w) { return T[kPairT1 + (w & 2047u)] ^ T[kPairT2 + ((w >> 11) & 2047u)] ^ T[kPairT3 + (w >> 22)]; };
-    auto a4 = [&](uint32_t w) {
-        const uint32_t* t4 = T + kPairA4;
-        return t4[w & 255u] ^ t4[256 + ((w >> 8) & 255u)] ^ t4[512 + ((w >> 16) & 255u)] ^ t4[768 + (w >> 24)];
-    };
     auto mulx = [](uint32_t b) { return (b >> 1) ^ (kPoly & (0u - (b & 1u))); };
     auto lanemul3 = [&](uint32_t a, uint32_t k) {  // the kernel's windowed multiply
         uint32_t m3[8], m2[4];
@@ -1747,129 +1200,48 @@ uint32_t zhip_emulate_chunk_crc_pair(const zhip_plan* plan, const uint8_t* data)
         for (int j = 1; j < 10; ++j) p = mulx(mulx(mulx(p))) ^ m3[(a >> (3 * j)) & 7u];
         return mulx(mulx(p)) ^ m2[a >> 30];
     };
-    const uint32_t N = (uint32_t)plan->layout.nbytes;
-    const uint32_t c96 = xpow8_inv(12);
-    uint32_t V = 0;
-    for (uint32_t s = 0; s < plan->nseg; ++s) {
-        const int32_t hi = (int32_t)plan->E - (int32_t)(s * plan->seg);
-        const int32_t lo = hi - (int32_t)plan->seg;
-        const uint32_t ku = gf_mul(xpow8((uint64_t)s * plan->seg), plan->c_inv);
-        for (int t = 0; t < kThreads; ++t) {
-            uint32_t a[4] = {0, 0, 0, 0};
-            for (int k = 0; k < (int)plan->kblocks; ++k) {
-                const int32_t o = lo + kWgStride * k + 16 * t;
-                uint8_t b[16] = {0};
-                for (int i = 0; i < 16; ++i) {
-                    const int64_t q = (int64_t)o + i;
-                    if (q >= 0 && q < (int64_t)N) b[i] = data[q];
-                }
-                uint32_t w[4];
-                std::memcpy(w, b, 16);
-                for (int j = 0; j < 4; ++j) a[j] = a11(a[j] ^ w[j]);
-            }
-            const uint32_t S = a4(a4(a4(a[0]) ^ a[1]) ^ a[2]) ^ a[3];
-            const uint32_t k11 = gf_mul(gf_mul(xpow8((uint64_t)kWgStride - 16u * t), ku), c96);
-            V ^= lanemul3(S, k11);
-        }
-    }
-    return ~(V ^ plan->c3);
+    const std::vector<uint32_t> h = build_row_tables(*plan);
+    const TabSet& S = plan->tl.pair;
+    return emulate_lanes(plan, data, &h[S.tab.off], &h[S.klane.off], S.klane.n, plan->kblocks,
+                         [&](int64_t i, int64_t k) {
+                             return (int64_t)plan->E - (i / kThreads + 1) * plan->seg + kWgStride * k + 16 * (i % kThreads);
+                         },
+                         lanemul3);
 }
 
-// CPU emulation of k_decode_il's CRC for one chunk: workgroup r takes steps
-// (r / S) S 8 + r % S + S k (k < 8); each lane's four word accumulators run
-// through the A_(4096 S) tables, fold with the A4 tables and are multiplied by
-// the workgroup's lane constant (windowed, as the kernel); -1 when the plan
-// has no interleaved layout.  Test hook.
+// k_decode_il's scheme: workgroup r takes steps (r / S) S 8 + r % S + S k
+// (k < 8) at the interleave the decode launches take (il_choose: the widest
+// built); 0xFFFFFFFF when the plan has no interleaved layout.  Test hook.
 uint32_t zhip_emulate_chunk_crc_il(const zhip_plan* plan, const uint8_t* data) {
-    std::call_once(g_once, init_tables);
     if (!plan || !plan->il_S) return 0xFFFFFFFFu;
-    // the interleave the decode launches take (zhip_decode_mapped): the widest
-    // that tiles the chunk's steps (the rule zhip_plan_upload builds tables by)
-    const uint32_t S = il_widest(plan);
-    const uint32_t K = kDefaultBlocks;
-    std::vector<uint32_t> tab(kPairTabWords);
-    build_pair_tables(tab.data(), (uint64_t)kWgStride * S);
-    const uint32_t* T = tab.data();
-    auto a11 = [&](uint32_t w) { return T[kPairT1 + (w & 2047u)] ^ T[kPairT2 + ((w >> 11) & 2047u)] ^ T[kPairT3 + (w >> 22)]; };
-    auto a4 = [&](uint32_t w) {
-        const uint32_t* t4 = T + kPairA4;
-        return t4[w & 255u] ^ t4[256 + ((w >> 8) & 255u)] ^ t4[512 + ((w >> 16) & 255u)] ^ t4[768 + (w >> 24)];
-    };
-    const uint32_t N = (uint32_t)plan->layout.nbytes;
-    const uint32_t c96 = xpow8_inv(12);
-    const int64_t n_steps = (int64_t)plan->nseg * K;
-    const int64_t lo_frame = (int64_t)plan->E - n_steps * kWgStride;
-    uint32_t V = 0;
-    for (uint32_t r = 0; r < plan->nseg; ++r) {
-        const int64_t st0 = (int64_t)(r / S) * S * K + (int64_t)(r % S);
-        for (int t = 0; t < kThreads; ++t) {
-            uint32_t a[4] = {0, 0, 0, 0};
-            for (uint32_t k = 0; k < K; ++k) {
-                const int64_t o = lo_frame + (int64_t)kWgStride * (st0 + (int64_t)S * k) + 16 * t;
-                uint8_t b[16] = {0};
-                for (int i = 0; i < 16; ++i) {
-                    const int64_t q = o + i;
-                    if (q >= 0 && q < (int64_t)N) b[i] = data[q];
-                }
-                uint32_t w[4];
-                std::memcpy(w, b, 16);
-                for (int j = 0; j < 4; ++j) a[j] = a11(a[j] ^ w[j]);
-            }
-            const uint32_t Sx = a4(a4(a4(a[0]) ^ a[1]) ^ a[2]) ^ a[3];
-            const int64_t e = (int64_t)kWgStride * (n_steps - st0 + 1 - (int64_t)S * K) - 16 * t;
-            const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-            V ^= gf_mul(Sx, gf_mul(gf_mul(xe, plan->c_inv), c96));
-        }
-    }
-    return ~(V ^ plan->c3);
+    const IlChoice c = il_choose(*plan, 0);
+    const int64_t S = c.S, K = kDefaultBlocks;
+    const int64_t lo_frame = (int64_t)plan->E - (int64_t)plan->nseg * K * kWgStride;
+    const std::vector<uint32_t> h = build_row_tables(*plan);
+    return emulate_lanes(plan, data, &h[c.set->tab.off], &h[c.set->klane.off], c.set->klane.n, (uint32_t)K,
+                         [&](int64_t i, int64_t k) {
+                             const int64_t r = i / kThreads, st0 = (r / S) * S * K + r % S;
+                             return lo_frame + kWgStride * (st0 + S * k) + 16 * (i % kThreads);
+                         },
+                         [](uint32_t a, uint32_t k) { return gf_mul(a, k); });
 }
 
-// CPU emulation of k_decode_xw's CRC for one chunk: lane l of span r takes
-// blocks at 8192 r + 1024 k + 16 l (k < 8) through the A_1024 tables, folds
-// with the A4 tables and multiplies by the (r, l) lane constant; -1 when the
-// plan has no xw layout.  Test hook.
+// k_decode_xw's scheme: lane l of span r takes blocks at 8192 r + 1024 k + 16 l
+// (k < 8); 0xFFFFFFFF when the plan has no xw layout.  Test hook.
 uint32_t zhip_emulate_chunk_crc_xw(const zhip_plan* plan, const uint8_t* data) {
-    std::call_once(g_once, init_tables);
     if (!plan || !plan->xw_P) return 0xFFFFFFFFu;
-    std::vector<uint32_t> tab(kPairTabWords);
-    build_pair_tables(tab.data(), 1024);
-    const uint32_t* T = tab.data();
-    auto a11 = [&](uint32_t w) { return T[kPairT1 + (w & 2047u)] ^ T[kPairT2 + ((w >> 11) & 2047u)] ^ T[kPairT3 + (w >> 22)]; };
-    auto a4 = [&](uint32_t w) {
-        const uint32_t* t4 = T + kPairA4;
-        return t4[w & 255u] ^ t4[256 + ((w >> 8) & 255u)] ^ t4[512 + ((w >> 16) & 255u)] ^ t4[768 + (w >> 24)];
-    };
-    const uint32_t N = (uint32_t)plan->layout.nbytes;
-    const uint32_t c96 = xpow8_inv(12);
-    const int64_t n_steps = (int64_t)plan->nseg * kDefaultBlocks;
-    const int64_t lo_frame = (int64_t)plan->E - n_steps * kWgStride;
-    uint32_t V = 0;
-    for (uint32_t r = 0; r < plan->xw_P; ++r)
-        for (int l = 0; l < 64; ++l) {
-            uint32_t a[4] = {0, 0, 0, 0};
-            for (int k = 0; k < kDefaultBlocks; ++k) {
-                const int64_t o = lo_frame + 8192 * (int64_t)r + 1024 * k + 16 * l;
-                uint8_t b[16] = {0};
-                for (int i = 0; i < 16; ++i) {
-                    const int64_t q = o + i;
-                    if (q >= 0 && q < (int64_t)N) b[i] = data[q];
-                }
-                uint32_t w[4];
-                std::memcpy(w, b, 16);
-                for (int j = 0; j < 4; ++j) a[j] = a11(a[j] ^ w[j]);
-            }
-            const uint32_t Sx = a4(a4(a4(a[0]) ^ a[1]) ^ a[2]) ^ a[3];
-            const int64_t e = (int64_t)kWgStride * (n_steps - 2 * (int64_t)r - 1) - 16 * l;
-            const uint32_t xe = e >= 0 ? xpow8((uint64_t)e) : xpow8_inv((uint64_t)(-e));
-            V ^= gf_mul(Sx, gf_mul(gf_mul(xe, plan->c_inv), c96));
-        }
-    return ~(V ^ plan->c3);
+    const int64_t lo_frame = (int64_t)plan->E - (int64_t)plan->nseg * kDefaultBlocks * kWgStride;
+    const std::vector<uint32_t> h = build_row_tables(*plan);
+    const TabSet& S = plan->tl.xw;
+    return emulate_lanes(plan, data, &h[S.tab.off], &h[S.klane.off], S.klane.n, kDefaultBlocks,
+                         [&](int64_t i, int64_t k) { return lo_frame + 8192 * (i / 64) + 1024 * k + 16 * (i % 64); },
+                         [](uint32_t a, uint32_t k) { return gf_mul(a, k); });
 }
 
 // CPU self-test of the identities the kernels rely on.  Returns 0 when all hold.
 int zhip_selftest(void) {
-    std::call_once(g_once, init_tables);
     // 1. top byte of T[i] is a bijection (needed for the inverse byte step)
+    const uint32_t* g_T = byte_tables().T;
     bool seen[256] = {false};
     for (int i = 0; i < 256; ++i) seen[g_T[i] >> 24] = true;
     for (int i = 0; i < 256; ++i)

@@ -151,7 +151,7 @@ __device__ __forceinline__ Unit advance_unit(const DecodeParams& p, const Unit& 
 }
 
 // The Horner operator tables [op][slice][256] (op k = A_(4096 - 4k), see
-// build_horner in capi.cpp) computed in LDS: entry b of (op, slice) is
+// fill_horner in plan_tables.cpp) computed in LDS: entry b of (op, slice) is
 // gf_mul(x_op, b << 8*slice), linear in b, so thread t = b xors the basis
 // values x_op * x^(31-j) (j = 8*slice + bit) of its set bits.  The basis chain
 // is wave-uniform (scalar ALU); no memory reads, so nothing here waits for the
@@ -376,7 +376,7 @@ __device__ __forceinline__ void retire(const DecodeParams& p, Pending& q, uint64
 }
 
 // ---- the pair kernel's CRC step (k_decode_pair / k_decode_il / k_decode_tile4f;
-// tables in the kPairTab* layout, built by capi.cpp build_pair_tables) ----
+// tables in the kPairTab* layout, built by plan_tables.cpp fill_pair_tables) ----
 struct Acc4 {
     uint32_t a0, a1, a2, a3;
 };

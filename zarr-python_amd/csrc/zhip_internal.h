@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/zarrhip.h"
+#include "zhip_plan_tables.h"
 
 namespace zhip {
 
@@ -548,11 +549,6 @@ EncodeFn select_encode_tileg_kernel(bool crc, int item, bool swap, EncTilegForm 
 
 }  // namespace zhip
 
-struct zhip_plan;
-namespace zhip {
-void fill_geom(Geom& g, const zhip_plan& plan);
-}
-
 struct zhip_plan {
     zhip_layout layout;
     uint32_t kblocks;  // K: blocks per thread per unit (4, 8 or 16)
@@ -567,80 +563,47 @@ struct zhip_plan {
     uint32_t row_bytes;
     zhip_fdiv drow;
     uint32_t fill[4];
+    // Everything but the next four fields is final after zhip_plan_create;
+    // zhip_plan_upload sets these.  The images' regions: tl (DESIGN.md "Plan
+    // table images").
     int device;
     int max_grid;
-    uint32_t* d_tables;  // horner (4096) | kthread (256) | kunit (nseg) | kpair (nseg * 256) |
-                         // pair tables (kPairTabWords) | kpair11 (nseg * 256) | kthread11 (256)
-    uint64_t off_pair;   // u32 offset of the pair tables in d_tables
+    uint32_t* d_tables;       // the row image
+    uint32_t* d_tile_tables;  // the tile image (tq >= 0)
+    zhip::TableLayout tl;
     // tile mode (layouts with a transposed dim that is contiguous in out)
     int32_t tq;          // -1: no tile mode
     uint32_t t_per_chunk, n_qb, n_cb;
     uint32_t sstride[ZHIP_MAX_DIMS];
     uint32_t t_c_inv;
-    // k_decode_tile4 (full tiles, groups of 4 tiles at a uniform base step):
-    // d_tile_tables continues with tz (1024: multiply by x^(8 step)) | kq4
-    // ((T/4) * 256: kthread * kunit[last tile of the group] * t_c_inv) | tmap (T)
+    // k_decode_tile4 (full tiles, groups of 4 tiles at a uniform base step)
     uint32_t tile4;
-    uint64_t tile4_step;                                 // base step between consecutive tiles
-    uint64_t tile4_off_tz, tile4_off_kq, tile4_off_map;  // u32 offsets in d_tile_tables
-    // k_decode_tile4f (tile step 256 B, CRC): A_64 tables in the kPairTab*
-    // layout | lane constants [T/4][kThreads], at tile4f_off in d_tile_tables
-    uint32_t tile4f;
-    uint64_t tile4f_off;
-    // k_decode_tile4w (tile4 layouts with a CRC): A_(4 sq) tables in the
-    // kPairTab* layout | lane constants [T/4][kThreads], at tile4w_off
-    uint32_t tile4w;
-    uint64_t tile4w_off;
-    uint64_t tile2w_off;  // lane constants [T/2][kThreads] of k_decode_tile4w's two-tile form (0: none)
-    uint64_t tile1w_off;  // tuning builds: lane constants [T][kThreads] of the one-tile form (0: none)
-    uint64_t tileg2w_off; // lane constants [2 n_groups][kThreads] of k_decode_tilegw's two-tile form (0: none)
-    uint64_t tilegl_off;  // tuning builds: lane constants [n_groups][kThreads] of its lane-tile form (0: none)
-    uint64_t tilebt_off;  // tuning builds: A_(4 sq) byte tables + A4 (kByteTabWords) for arms 66 / 67 (0: none)
-    uint64_t tile2e_off;  // lane constants [T/2][kThreads] of k_encode_tile4's two-tile form (0: none)
+    uint64_t tile4_step;  // base step between consecutive tiles
+    uint32_t tile4f;      // k_decode_tile4f (tile step 256 B, CRC)
+    uint32_t tile4w;      // k_decode_tile4w (tile4 layouts with a CRC)
     // full-tile layouts that tile4 declines (e.g. 128^3 chunks: the four tiles
     // of a natural group at two steps) but whose consecutive tile pairs are the
     // two column blocks of one row band: k_decode_tile4w<2> over pairs (2 k,
-    // 2 k + 1), tuning arm 39; d_tile_tables at tile2_off (tuning builds): A_(4 sq)
-    // pair tables | tile map (T TileEnt) | lane constants [T/2][kThreads]
+    // 2 k + 1), tuning arm 39
     uint32_t tile2;
-    uint64_t tile2_off;
     // the whole-chunk row map of a whole-row layout in two-level affine form
     // (plan_affine; ZHIP_DF_WHOLE launches): aff_ok, shift, B, C, D
     uint32_t aff_ok, aff_sh;
     int32_t aff_B, aff_C, aff_D;
-    // k_decode_tilegw (grouped tile layouts with a CRC): the same for groups
-    uint32_t tilegw;
-    uint64_t tilegw_off;
+    uint32_t tilegw;  // k_decode_tilegw (grouped tile layouts with a CRC)
     // k_encode_tileg (full selections): tiles grouped by four along the
     // innermost other stored dim gd with shape[gd] % 4 == 0 (uniform step
-    // sstride[gd] inside every group, whatever the natural tile order); tables
-    // tzg (1024: multiply by x^(8 sstride[gd])) | gmap (n_groups GroupEnt)
+    // sstride[gd] inside every group, whatever the natural tile order)
     int32_t gd;                      // -1: no such dim
     uint32_t n_groups;
     uint32_t n_sub;                  // > 16 groups per chunk: arrival subgroups of 16 (workspace tail)
-    uint64_t g_off_tz, g_off_map;    // u32 offsets in d_tile_tables
-    uint32_t* d_tile_tables;
     // shard index (sharded layouts): payload 16*n_inner, E, CRC constants
-    uint32_t idx_nbytes, idx_E, idx_c_inv, idx_c3;  // horner (stride 16*sstride[tq]) | kthread (256) | kunit (t_per_chunk)
+    uint32_t idx_nbytes, idx_E, idx_c_inv, idx_c3;
     // k_decode_il (interleaved steps, decode_rows.hip): a workgroup takes K = 8
     // of the chunk's 4 KiB steps at a stride of il_S steps (il_S = 0: not
-    // available for this layout).  d_tables continues at off_il with the
-    // 11/11/10 tables of A_(4096 il_S) (kPairTabWords) | klane (nseg x 256:
-    // per workgroup-in-chunk lane constants) | kidx (256: the fused index
-    // check's lane constants under those tables)
+    // available for this layout)
     uint32_t il_S;
-    uint64_t off_il;
     // k_decode_xw (decode_rows.hip): xw_P = 8 KiB spans per chunk (0: not
-    // available), xw_nsub = two-level arrival subwords (P > 32, P <= 1024).
-    // d_tables continues at off_xw with the tables of A_1024 | klane (P x 64) |
-    // kidx (256)
+    // available), xw_nsub = two-level arrival subwords (P > 32, P <= 1024)
     uint32_t xw_P, xw_nsub;
-    uint64_t off_xw;
-    // k_decode_ilw (decode_rows.hip): one 32 KiB unit per workgroup of NT =
-    // 512 / 1024 lanes (2048 / NT blocks per lane); d_tables continues at
-    // off_ilw[0] (NT = 1024) / off_ilw[1] (NT = 512) with the tables of
-    // A_(16 NT) | klane (nseg x NT) | kidx (256); 0: not built
-    uint64_t off_ilw[2];
-    uint64_t off_ilh;
-    uint64_t off_il_s[2];  // tuning builds: k_decode_il's tables for S = 16 / 32 (arms 69 / 70; 0: none)  // tuning builds: k_decode_ilh's lane constants [2 nseg][kThreads] (0: none)
 };

@@ -314,6 +314,10 @@ def lib():
     L.zhip_emulate_chunk_crc_il.restype = ctypes.c_uint32
     L.zhip_emulate_chunk_crc_xw.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.zhip_emulate_chunk_crc_xw.restype = ctypes.c_uint32
+    L.zhip_plan_table_image.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64]
+    L.zhip_plan_table_image.restype = ctypes.c_uint64
+    L.zhip_plan_table_offsets.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+    L.zhip_plan_table_offsets.restype = ctypes.c_uint32
     L.zhip_fdiv_eval.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.zhip_fdiv_eval.restype = ctypes.c_uint32
     L.zhip_tuning_build.restype = ctypes.c_int
@@ -388,6 +392,21 @@ class Plan:
         fn = lib().zhip_emulate_chunk_crc_il if pair == "il" else lib().zhip_emulate_chunk_crc_xw if pair == "xw" else \
             lib().zhip_emulate_chunk_crc_pair if pair else lib().zhip_emulate_chunk_crc
         return int(fn(self._h, buf))
+
+    def table_image(self, which: int) -> np.ndarray:
+        """The table image zhip_plan_upload puts on the device, built on the host
+        (0: row tables, 1: tile tables; empty where the plan has none).  Test hook."""
+        n = int(lib().zhip_plan_table_image(self._h, which, None, 0))
+        out = np.zeros(n, np.uint32)
+        assert int(lib().zhip_plan_table_image(self._h, which, out.ctypes.data, n)) == n
+        return out
+
+    def table_regions(self) -> tuple[list[int], list[int]]:
+        """(word offsets, word counts) of the images' regions in the library's order.  Test hook."""
+        n = int(lib().zhip_plan_table_offsets(self._h, None, 0))
+        out = np.zeros(2 * n, np.uint64)
+        assert int(lib().zhip_plan_table_offsets(self._h, out.ctypes.data, 2 * n)) == n
+        return [int(v) for v in out[:n]], [int(v) for v in out[n:]]
 
     def __del__(self):
         h = getattr(self, "_h", None)
