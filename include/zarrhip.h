@@ -727,6 +727,134 @@ int zhip_points_fill(const zhip_points_geom *geom, const int64_t *const *d_coord
 int zhip_emulate_points(const zhip_points_geom *geom, const int64_t *const *coords, uint64_t n,
                         uint32_t *counts, uint32_t *err, uint32_t *first, uint32_t *cursor, int64_t *table);
 
+/* ---- element-wise value codecs: scale_offset and cast_value ----
+ *
+ * zhip_value_map replaces ScaleOffset._decode_sync / _encode_sync
+ * (src/zarr/codecs/scale_offset.py:379-415, arithmetic at :220-279) and
+ * CastValue._decode_sync / _encode_sync (src/zarr/codecs/cast_value.py:380-418)
+ * for the value part [scale_offset], [cast_value] or [scale_offset, cast_value]
+ * of a chain ("packed" arrays: floats kept as small integers with a scale and
+ * an offset).  One side of the map holds the array dtype, the other the stored
+ * dtype:
+ *   decode  a = stored elements, b = array elements:  cast back, then x / scale + offset
+ *   encode  a = array elements,  b = stored elements: (x - offset) * scale, then cast
+ *
+ * scale_offset runs in the array dtype.  Floats: one IEEE operation at a time
+ * in that float type (never contracted).  Integers: exact arithmetic; decode
+ * needs x % scale == 0 (else ZHIP_VE_INEXACT) and a result outside the dtype's
+ * range is ZHIP_VE_SO_RANGE.
+ *
+ * cast_value: (1) a scalar_map entry of this direction whose key equals the
+ * input gives its value as is (a NaN key matches every NaN, +0 == -0, no
+ * rounding, no range check); (2) a float going to an integer is rounded to an
+ * integer in its own format by `rounding`; NaN is ZHIP_VE_NAN; (3) a value
+ * outside the target's range is ZHIP_VE_CAST_RANGE with ZHIP_VO_ERROR, goes to
+ * the nearest end with ZHIP_VO_CLAMP (+-inf too), or is reduced modulo 2^bits
+ * with ZHIP_VO_WRAP (+-inf is ZHIP_VE_CAST_RANGE); integer -> float is exact for
+ * every pair accepted.  An element with an error writes zero bits.
+ *
+ * Accepted (array -> stored): float32 -> int8/uint8/int16/uint16; float64 ->
+ * those and int32/uint32; any of int8/16/32/64, uint8/16/32 -> any other of
+ * them.  scale_offset: float32, float64, int8/16/32, uint8/16/32. */
+#define ZHIP_VT_I8 0u
+#define ZHIP_VT_U8 1u
+#define ZHIP_VT_I16 2u
+#define ZHIP_VT_U16 3u
+#define ZHIP_VT_I32 4u
+#define ZHIP_VT_U32 5u
+#define ZHIP_VT_I64 6u
+#define ZHIP_VT_F32 7u
+#define ZHIP_VT_F64 8u
+
+#define ZHIP_VS_SCALE_OFFSET 1u   /* zhip_value_op.stages */
+#define ZHIP_VS_CAST 2u
+
+#define ZHIP_VR_NEAREST_EVEN 0u   /* zhip_value_op.rounding */
+#define ZHIP_VR_TOWARDS_ZERO 1u
+#define ZHIP_VR_TOWARDS_POSITIVE 2u
+#define ZHIP_VR_TOWARDS_NEGATIVE 3u
+#define ZHIP_VR_NEAREST_AWAY 4u
+
+#define ZHIP_VO_ERROR 0u          /* zhip_value_op.out_of_range */
+#define ZHIP_VO_CLAMP 1u
+#define ZHIP_VO_WRAP 2u
+
+#define ZHIP_VE_INEXACT 1u        /* error word bits: scale_offset decode remainder       */
+#define ZHIP_VE_SO_RANGE 2u       /* scale_offset result outside the dtype's range        */
+#define ZHIP_VE_CAST_RANGE 4u     /* cast_value input outside the target's range          */
+#define ZHIP_VE_NAN 8u            /* cast_value: NaN to an integer without a map entry    */
+
+#define ZHIP_VALUE_MAX_MAP 8u
+#define ZHIP_VALUE_TILE 2048u     /* elements of one workgroup (256 lanes x 8); a tile never spans two items */
+
+/* Launch-uniform description of the map.  Scalars are raw bits in the low
+ * bytes of a uint64 (an int8 -1 is 0xff). */
+typedef struct zhip_value_op {
+    uint32_t encode;        /* 0 decode (a stored, b array), 1 encode (a array, b stored) */
+    uint32_t array_dt;      /* ZHIP_VT_*                                                  */
+    uint32_t stored_dt;     /* = array_dt without ZHIP_VS_CAST                            */
+    uint32_t stages;        /* ZHIP_VS_* present                                          */
+    uint64_t offset, scale; /* array dtype                                                */
+    uint32_t rounding;      /* ZHIP_VR_*                                                  */
+    uint32_t out_of_range;  /* ZHIP_VO_*                                                  */
+    uint32_t n_map;         /* scalar_map entries of this direction, <= ZHIP_VALUE_MAX_MAP */
+    uint32_t fill_nan;      /* the array fill is a NaN (any NaN equals it)                */
+    uint64_t map_key[ZHIP_VALUE_MAX_MAP];  /* the cast's input dtype  */
+    uint64_t map_val[ZHIP_VALUE_MAX_MAP];  /* the cast's output dtype */
+    uint64_t fill;          /* the array fill value, array dtype                          */
+} zhip_value_op;            /* 184 bytes */
+
+#define ZHIP_VI_MISSING 1u  /* decode: write the array fill, read nothing                 */
+#define ZHIP_VI_STATUS 2u   /* decode: the same when d_status[status].code == ZHIP_ST_MISSING */
+
+typedef struct zhip_value_dim {
+    int64_t sa, sb;         /* byte strides on the a and the b side (any sign, sa may be 0) */
+    uint32_t count;         /* >= 1 */
+    uint32_t _pad;
+    zhip_fdiv div;          /* division by count */
+} zhip_value_dim;           /* 32 bytes */
+
+/* A product of up to ZHIP_MAX_DIMS dimensions, elements numbered with the
+ * LAST dimension fastest: element (k_0 .. k_{n-1}) is read at a + a_base +
+ * sum k_d sa_d and written at b + b_base + sum k_d sb_d. */
+typedef struct zhip_value_item {
+    int64_t a_base, b_base;
+    uint32_t ndim;          /* 1 .. ZHIP_MAX_DIMS */
+    uint32_t total;         /* prod(count) < 2^31 */
+    uint32_t flags;         /* ZHIP_VI_* */
+    uint32_t status;        /* index into d_status with ZHIP_VI_STATUS */
+    zhip_value_dim dims[ZHIP_MAX_DIMS];
+} zhip_value_item;          /* 288 bytes */
+
+/* One launch over every item.  d_tile_prefix as for zhip_select_copy, with
+ * ZHIP_VALUE_TILE elements per tile.  a / b are aligned to their item sizes and
+ * do not overlap; a_size / b_size are the bytes readable at a / writable at b:
+ * THE CALLER CHECKS EVERY ITEM AGAINST THEM, the kernel only skips what falls
+ * outside as a second fence.  d_err: one word, bits ZHIP_VE_* are ORed into it
+ * (the caller zeroes it).  d_nonempty (encode only, may be null): one zeroed
+ * word per item, set to 1 when any array-side element differs from the fill by
+ * the rule of NDBuffer.all_equal (bitwise; any NaN equals a NaN fill).
+ * d_status may be null when no item has ZHIP_VI_STATUS.  An item whose
+ * innermost dimension is contiguous on both sides, with a count that is a
+ * multiple of the lane's vector width and vector-aligned rows, moves 16 bytes
+ * per lane access on its narrow side (8 bytes for 1-byte items); any other
+ * item goes element by element.  Asynchronous on `stream`; afterwards
+ * zhip_last_kernel() is "k_value_map". */
+int zhip_value_map(const zhip_value_op *op, const zhip_value_item *d_items, uint32_t n_items,
+                   const uint32_t *d_tile_prefix, uint32_t n_tiles, const zhip_status *d_status,
+                   const void *a, uint64_t a_size, void *b, uint64_t b_size, uint32_t *d_err,
+                   uint32_t *d_nonempty, void *stream);
+/* CPU-only test hook and the host's one statement of the arithmetic (the
+ * codec classes cast and encode fill values through it): the same items, the
+ * same per-element function, over host memory.  Validates the op and the item
+ * tables (ZHIP_E_INVALID / ZHIP_E_UNSUPPORTED); ZHIP_E_BOUNDS, mapping nothing
+ * further, at the first element outside a_size / b_size.  n_status: records
+ * at status. */
+int zhip_emulate_value_map(const zhip_value_op *op, const zhip_value_item *items, uint32_t n_items,
+                           const uint32_t *tile_prefix, uint32_t n_tiles, const zhip_status *status,
+                           uint32_t n_status, const void *a, uint64_t a_size, void *b, uint64_t b_size,
+                           uint32_t *err, uint32_t *nonempty);
+
 /* Host CRC-32C (reflected 0x82F63B78, init / xorout 0xFFFFFFFF) of nbytes at
  * data: the host stage of a chain, where the bytes never reach the GPU -- a
  * crc32c after a host-side compressor (Crc32cCodec._decode_sync / _encode_sync,

@@ -17,6 +17,7 @@
 #include "zhip_internal.h"
 #include "zhip_points.h"
 #include "zhip_select.h"
+#include "zhip_values.h"
 
 using namespace zhip;
 
@@ -1005,6 +1006,45 @@ int zhip_emulate_select_copy(const zhip_select_item* items, uint32_t n_items, co
             }
     }
     return ZHIP_OK;
+}
+
+// ---- zhip_value_map: scale_offset / cast_value (values.hip, value_map.cpp) ----
+static int value_args(const zhip_value_op* op, uint32_t n_items, const void* items, const void* prefix,
+                      const void* a, const void* b, const void* err) {
+    const char* msg = "";
+    const int rc = value_check_op(op, &msg);
+    if (rc != ZHIP_OK) return set_err(rc, msg);
+    if (!n_items || !items || !prefix || !a || !b || !err) return set_err(ZHIP_E_INVALID, "null argument");
+    if (((uintptr_t)a & (vt_size(value_a_dt(*op)) - 1)) || ((uintptr_t)b & (vt_size(value_b_dt(*op)) - 1)))
+        return set_err(ZHIP_E_INVALID, "a / b not aligned to their item sizes");
+    return ZHIP_OK;
+}
+
+int zhip_value_map(const zhip_value_op* op, const zhip_value_item* d_items, uint32_t n_items,
+                   const uint32_t* d_tile_prefix, uint32_t n_tiles, const zhip_status* d_status, const void* a,
+                   uint64_t a_size, void* b, uint64_t b_size, uint32_t* d_err, uint32_t* d_nonempty,
+                   void* stream) {
+    if (n_tiles == 0) return ZHIP_OK;
+    const int rc = value_args(op, n_items, d_items, d_tile_prefix, a, b, d_err);
+    if (rc != ZHIP_OK) return rc;
+    if (n_tiles > 0x7fffffffu) return set_err(ZHIP_E_UNSUPPORTED, "too many tiles for one launch");
+    const int e = value_launch(*op, d_items, n_items, d_tile_prefix, n_tiles, d_status, a, a_size, b, b_size,
+                               d_err, d_nonempty, stream);
+    if (e != 0) return set_err(ZHIP_E_HIP, std::string("k_value_map launch: ") + hipGetErrorString((hipError_t)e));
+    return ZHIP_OK;
+}
+
+int zhip_emulate_value_map(const zhip_value_op* op, const zhip_value_item* items, uint32_t n_items,
+                           const uint32_t* tile_prefix, uint32_t n_tiles, const zhip_status* status,
+                           uint32_t n_status, const void* a, uint64_t a_size, void* b, uint64_t b_size,
+                           uint32_t* err, uint32_t* nonempty) {
+    if (n_tiles == 0) return ZHIP_OK;
+    int rc = value_args(op, n_items, items, tile_prefix, a, b, err);
+    if (rc != ZHIP_OK) return rc;
+    const char* msg = "";
+    rc = value_emulate(*op, items, n_items, tile_prefix, n_tiles, status, n_status, a, a_size, b, b_size, err,
+                       nonempty, &msg);
+    return rc == ZHIP_OK ? rc : set_err(rc, msg);
 }
 
 // ---- zhip_points_count / zhip_points_fill: device-built point tables (points.hip) ----

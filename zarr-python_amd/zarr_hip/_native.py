@@ -185,6 +185,23 @@ SELECT_ITEM_DT = np.dtype([("a_base", "<i8"), ("b_base", "<i8"), ("ndim", "<u4")
                            ("_pad", "<u4", (2,)), ("dims", SELECT_DIM_DT, (MAX_DIMS,))])
 assert SELECT_DIM_DT.itemsize == 64 and SELECT_ITEM_DT.itemsize == 544
 
+# zhip_value_op / zhip_value_dim / zhip_value_item (include/zarrhip.h): zhip_value_map
+VALUE_TILE = 2048
+VALUE_MAX_MAP = 8
+VT_I8, VT_U8, VT_I16, VT_U16, VT_I32, VT_U32, VT_I64, VT_F32, VT_F64 = range(9)
+VS_SCALE_OFFSET, VS_CAST = 1, 2
+VO_ERROR, VO_CLAMP, VO_WRAP = 0, 1, 2
+VE_INEXACT, VE_SO_RANGE, VE_CAST_RANGE, VE_NAN = 1, 2, 4, 8
+VI_MISSING, VI_STATUS = 1, 2
+VALUE_OP_DT = np.dtype([("encode", "<u4"), ("array_dt", "<u4"), ("stored_dt", "<u4"), ("stages", "<u4"),
+                        ("offset", "<u8"), ("scale", "<u8"), ("rounding", "<u4"), ("out_of_range", "<u4"),
+                        ("n_map", "<u4"), ("fill_nan", "<u4"), ("map_key", "<u8", (VALUE_MAX_MAP,)),
+                        ("map_val", "<u8", (VALUE_MAX_MAP,)), ("fill", "<u8")])
+VALUE_DIM_DT = np.dtype([("sa", "<i8"), ("sb", "<i8"), ("count", "<u4"), ("_pad", "<u4"), ("div", "<u4", (2,))])
+VALUE_ITEM_DT = np.dtype([("a_base", "<i8"), ("b_base", "<i8"), ("ndim", "<u4"), ("total", "<u4"),
+                          ("flags", "<u4"), ("status", "<u4"), ("dims", VALUE_DIM_DT, (MAX_DIMS,))])
+assert VALUE_OP_DT.itemsize == 184 and VALUE_DIM_DT.itemsize == 32 and VALUE_ITEM_DT.itemsize == 288
+
 # zhip_points_geom and the limits of zhip_points_count / zhip_points_fill (include/zarrhip.h)
 POINTS_MAX_N = 0x7FFFFFFF
 POINTS_MAX_DIM = 0x7FFFFFFF
@@ -325,6 +342,10 @@ def lib():
     L.zhip_select_copy.restype = ctypes.c_int
     L.zhip_emulate_select_copy.argtypes = [vp, u32, vp, u64, vp, u32, vp, u64, vp, u64, u32]
     L.zhip_emulate_select_copy.restype = ctypes.c_int
+    L.zhip_value_map.argtypes = [vp, vp, u32, vp, u32, vp, vp, u64, vp, u64, vp, vp, vp]
+    L.zhip_value_map.restype = ctypes.c_int
+    L.zhip_emulate_value_map.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, u64, vp, u64, vp, vp]
+    L.zhip_emulate_value_map.restype = ctypes.c_int
     L.zhip_points_count.argtypes = [vp, vp, u64, vp, vp, vp]
     L.zhip_points_count.restype = ctypes.c_int
     L.zhip_points_fill.argtypes = [vp, vp, u64, vp, vp, vp, vp]

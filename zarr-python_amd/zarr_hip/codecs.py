@@ -446,6 +446,255 @@ class HostCodec:
         return _to_bytes(out)
 
 
+def _native_dt(dtype) -> np.dtype:
+    """numpy dtype of a numpy dtype, a name or zarr's ZDType."""
+    if hasattr(dtype, "to_native_dtype"):
+        dtype = dtype.to_native_dtype()
+    return np.dtype(dtype)
+
+
+@dataclass(frozen=True)
+class ScaleOffsetCodec:
+    """scale_offset.py:282-418: encode (x - offset) * scale, decode x / scale +
+    offset, in the array's own dtype.  The arithmetic runs in k_value_map
+    (values.py); fill values go through the same function on the host."""
+
+    offset: Any = 0
+    scale: Any = 1
+    is_fixed_size = True
+    kind = "AA"
+    value_codec = True
+
+    def __post_init__(self):
+        for name in ("offset", "scale"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, str)):
+                raise TypeError(f"{name} must be a number or string, got {type(v).__name__}")
+
+    @classmethod
+    def from_dict(cls, data: Any) -> "ScaleOffsetCodec":
+        return cls(**_named(data, "scale_offset"))
+
+    def to_dict(self) -> dict:
+        config = {}
+        if self.offset != 0:
+            config["offset"] = self.offset
+        if self.scale != 1:
+            config["scale"] = self.scale
+        return {"name": "scale_offset", "configuration": config} if config else {"name": "scale_offset"}
+
+    def parsed(self, dtype) -> tuple:
+        """(offset, scale) as scalars of the array dtype (from_json_scalar)."""
+        from .values import parse_scalar
+
+        native = _native_dt(dtype)
+        out = []
+        for name, value in (("offset", self.offset), ("scale", self.scale)):
+            try:
+                out.append(parse_scalar(value, native))
+            except (TypeError, ValueError, OverflowError) as e:
+                raise ValueError(
+                    f"scale_offset {name} value {value!r} is not representable in dtype {native}.") from e
+        return tuple(out)
+
+    def _served(self, native: np.dtype) -> None:
+        from .values import SCALE_OFFSET_DTYPES
+
+        if native.kind not in "iuf":
+            raise ValueError("scale_offset codec only supports integer and floating-point data types. "
+                             f"Got {native}.")
+        if native.name not in SCALE_OFFSET_DTYPES:
+            raise NotImplementedError(
+                f"scale_offset: dtype {native} is outside the served table {SCALE_OFFSET_DTYPES} "
+                "(64-bit integers need arithmetic wider than int64; float16 is not built)")
+
+    def validate(self, *, dtype=None, **kw) -> None:
+        if dtype is None:
+            return
+        native = _native_dt(dtype)
+        self._served(native)
+        if self.parsed(native)[1] == 0:
+            raise ValueError("scale_offset scale must be non-zero.")
+
+    def evolve_from_array_spec(self, spec: ArraySpec) -> "ScaleOffsetCodec":
+        return self
+
+    def resolve_metadata(self, spec: ArraySpec) -> ArraySpec:
+        """scale_offset.py:371-377: the dtype stays, the fill becomes encode(fill)."""
+        from . import values
+
+        self.validate(dtype=spec.dtype)
+        fill = 0 if spec.fill_value is None else spec.fill_value
+        op = values.make_op(True, spec.dtype, spec.dtype, self.parsed(spec.dtype), None, fill)
+        try:
+            new = values.map_scalar(op, np.asarray(fill).astype(spec.dtype), "scale_offset")
+        except ValueError as e:
+            info = np.iinfo(spec.dtype)
+            raise ValueError(f"scale_offset produced a value outside the range of dtype {spec.dtype} "
+                             f"[{info.min}, {info.max}].") from e
+        return replace(spec, fill_value=new.item())
+
+    def compute_encoded_size(self, n: int, spec: ArraySpec | None = None) -> int:
+        return n
+
+
+_CAST_PERMITTED = {
+    "int2", "int4", "int8", "int16", "int32", "int64", "uint2", "uint4", "uint8", "uint16", "uint32", "uint64",
+    "float4_e2m1fn", "float6_e2m3fn", "float6_e3m2fn", "float8_e3m4", "float8_e4m3", "float8_e4m3b11fnuz",
+    "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz", "float8_e8m0fnu", "bfloat16", "float16", "float32",
+    "float64"}  # cast_value.py:59-100
+from .values import ROUNDING as _CAST_ROUNDING  # noqa: E402  (one statement of the modes, in op-record order)
+
+
+def _dtype_name(dt) -> str:
+    if isinstance(dt, str):
+        return dt
+    if hasattr(dt, "to_json"):
+        j = dt.to_json(zarr_format=3)
+        return j if isinstance(j, str) else str(j.get("name"))
+    return np.dtype(dt.to_native_dtype() if hasattr(dt, "to_native_dtype") else dt).name
+
+
+@dataclass(frozen=True)
+class CastValueCodec:
+    """cast_value.py:183-435: elements stored in another dtype, with a rounding
+    mode, an out-of-range mode and explicit scalar maps per direction.  The
+    cast runs in k_value_map (values.py); its rules are include/zarrhip.h's."""
+
+    data_type: Any
+    rounding: str = "nearest-even"
+    out_of_range: str | None = None
+    scalar_map: Any = None  # normalised: (("encode", ((key, value), ...)), ("decode", (...)))
+    is_fixed_size = True
+    kind = "AA"
+    value_codec = True
+
+    def __post_init__(self):
+        name = _dtype_name(self.data_type)
+        if name not in _CAST_PERMITTED:
+            raise ValueError(f"Invalid target data type {self.data_type!r}. cast_value codec only supports "
+                             f"integer and floating-point data types. Got {name}.")
+        object.__setattr__(self, "data_type", name)
+        if self.rounding not in _CAST_ROUNDING:
+            raise ValueError(f"cast_value: rounding must be one of {_CAST_ROUNDING}. Got {self.rounding!r}.")
+        if self.out_of_range not in (None, "clamp", "wrap"):
+            raise ValueError(f"cast_value: out_of_range must be None, 'clamp' or 'wrap'. Got {self.out_of_range!r}.")
+        sm = self.scalar_map
+        if sm is not None:
+            if not isinstance(sm, dict):
+                sm = dict(sm)
+            norm = []
+            for direction in ("encode", "decode"):
+                entries = sm.get(direction)
+                if entries is not None:
+                    pairs = entries.items() if hasattr(entries, "items") else entries
+                    norm.append((direction, tuple((k, v) for k, v in pairs)))
+            object.__setattr__(self, "scalar_map", tuple(norm))
+
+    @classmethod
+    def from_dict(cls, data: Any) -> "CastValueCodec":
+        conf = _named(data, "cast_value")
+        if "data_type" not in conf:
+            raise ValueError("cast_value requires a configuration with `data_type`.")
+        return cls(**conf)
+
+    def to_dict(self) -> dict:
+        """cast_value.py:267-279: the defaults are omitted."""
+        config: dict = {"data_type": self.data_type}
+        if self.rounding != "nearest-even":
+            config["rounding"] = self.rounding
+        if self.out_of_range is not None:
+            config["out_of_range"] = self.out_of_range
+        if self.scalar_map is not None:
+            config["scalar_map"] = {d: [(k, v) for k, v in pairs] for d, pairs in self.scalar_map}
+        return {"name": "cast_value", "configuration": config}
+
+    def _map(self, direction: str) -> tuple:
+        return dict(self.scalar_map or ()).get(direction, ())
+
+    def target(self) -> np.dtype:
+        try:
+            return np.dtype(self.data_type)
+        except TypeError:
+            raise NotImplementedError(
+                f"cast_value: target dtype {self.data_type} is outside the served table (no such numpy dtype)") from None
+
+    def _served(self, source: np.dtype) -> None:
+        from .values import cast_pair_ok
+
+        if not cast_pair_ok(source, self.target()):
+            raise NotImplementedError(
+                f"cast_value: {source} stored as {self.data_type} is outside the served table (float32 -> "
+                "int8/uint8/int16/uint16, float64 -> those and int32/uint32, any of int8/16/32/64 and "
+                "uint8/16/32 -> another of them): only pairs whose decode direction is exact are built")
+
+    def op_fields(self, array_dt, encode: bool) -> dict:
+        """rounding / out_of_range / this direction's map entries as scalars of
+        the cast's input and output dtypes."""
+        from .values import parse_scalar
+
+        array_dt = _native_dt(array_dt)
+        direction = "encode" if encode else "decode"
+        kd, vd = (array_dt, self.target()) if encode else (self.target(), array_dt)
+        pairs = []
+        for k, v in self._map(direction):
+            out = []
+            for label, value, dt in (("key", k, kd), ("value", v, vd)):
+                try:
+                    out.append(parse_scalar(value, dt))
+                except (TypeError, ValueError, OverflowError) as e:
+                    raise ValueError(
+                        f"scalar_map {direction} {label} {value!r} is not representable in dtype {dt}.") from e
+            pairs.append(tuple(out))
+        if len(pairs) > 8:
+            raise NotImplementedError(
+                f"cast_value: more than 8 scalar_map entries per direction ({len(pairs)} for {direction})")
+        return {"rounding": self.rounding, "out_of_range": self.out_of_range, "map": pairs}
+
+    def validate(self, *, dtype=None, **kw) -> None:
+        """cast_value.py:281-329, then the served table."""
+        if dtype is None:
+            return
+        src = _dtype_name(dtype) if not isinstance(dtype, np.dtype) else dtype.name
+        if src not in _CAST_PERMITTED:
+            raise ValueError("The cast_value codec only supports integer and floating-point data types. "
+                             f"Got source dtype {src}.")
+        if self.out_of_range == "wrap" and not self.data_type.lstrip("u").startswith("int"):
+            raise ValueError("out_of_range='wrap' is only valid for integer target types. "
+                             f"Got target dtype {self.data_type}.")
+        native = _native_dt(dtype)
+        self._served(native)
+        for encode in (True, False):
+            self.op_fields(native, encode)
+
+    def evolve_from_array_spec(self, spec: ArraySpec) -> "CastValueCodec":
+        return self
+
+    def resolve_metadata(self, spec: ArraySpec) -> ArraySpec:
+        """cast_value.py:362-378: dtype and fill become the cast of the fill; a
+        fill that cannot be cast raises here."""
+        from . import values
+
+        self.validate(dtype=spec.dtype)
+        fill = 0 if spec.fill_value is None else spec.fill_value
+        op = values.make_op(True, spec.dtype, self.target(), None, self.op_fields(spec.dtype, True), fill)
+        try:
+            new = values.map_scalar(op, np.asarray(fill).astype(spec.dtype), "cast_value")
+        except ValueError as e:
+            raise ValueError(f"cast_value: the fill value {fill!r} of dtype {spec.dtype} cannot be cast to "
+                             f"{self.data_type} (out of range or not a number)") from e
+        return replace(spec, dtype=self.target(), fill_value=new.item())
+
+    def compute_encoded_size(self, n: int, spec: ArraySpec | None = None) -> int:
+        if spec is None:
+            raise ValueError("cast_value: compute_encoded_size needs the chunk spec")
+        return n // np.dtype(spec.dtype).itemsize * self.target().itemsize
+
+
+def is_value_codec(c) -> bool:
+    return getattr(c, "value_codec", False) is True
+
+
 @dataclass(frozen=True)
 class ForeignArrayCodec:
     """A caller's array->array codec instance other than ``transpose`` (e.g. a
@@ -605,6 +854,8 @@ _REGISTRY = {
     "transpose": TransposeCodec,
     "sharding_indexed": ShardingCodec,
     "gzip": GzipCodec,
+    "scale_offset": ScaleOffsetCodec,
+    "cast_value": CastValueCodec,
 }
 
 
@@ -618,7 +869,7 @@ def parse_codecs(codecs) -> list:
     out = []
     for c in codecs:
         if isinstance(c, (BytesCodec, Crc32cCodec, TransposeCodec, ShardingCodec, GzipCodec, HostCodec, V2Stage,
-                          ForeignArrayCodec)):
+                          ForeignArrayCodec, ScaleOffsetCodec, CastValueCodec)):
             out.append(c)
             continue
         if is_v2_codec(c):  # zarr v2's filters + compressor wrapper (an ArrayBytesCodec)
@@ -626,6 +877,9 @@ def parse_codecs(codecs) -> list:
             continue
         conf = c.to_dict() if hasattr(c, "to_dict") and not isinstance(c, dict) else c
         name = conf if isinstance(conf, str) else conf["name"]
+        if name in ("scale_offset", "cast_value") and not isinstance(c, (dict, str)) and codec_kind(c) == "AA":
+            out.append(_REGISTRY[name].from_dict(conf))  # zarr's ScaleOffset / CastValue: served (values.py)
+            continue
         if name != "transpose" and not isinstance(c, (dict, str)) and codec_kind(c) == "AA":
             out.append(ForeignArrayCodec(c))  # spec threading only; not on the GPU path
             continue

@@ -523,9 +523,11 @@ def _one_spec(batch, fancy):
 
 
 def _direct(pipe) -> bool:
-    """One device, no nesting, no host stage: the box decode is planned and
+    """One device, no nesting, no host stage, no value codecs: the box decode is planned and
     launched here, back to back with the gather; every other route composes
     through the public read_sync / _write_sync (an extra synchronisation)."""
+    if pipe._value_split() is not None:  # value codecs: the scratch is array-dtype, through read_sync
+        return False
     return len(pipe.devices) <= 1 and pipe._nested() is None and pipe._host_split() is None
 
 

@@ -1137,6 +1137,18 @@ class HipCodecPipeline:
                 aux["split"] = (outer, inner, read_pipe, self._sub(wfixed))
         return aux["split"]
 
+    def _value_split(self):
+        """None for a chain without value codecs (scale_offset / cast_value),
+        else values.split's (scale_offset, cast_value, stored pipeline,
+        sharded): the stored pipeline is this chain without them, used with
+        the chunk spec's dtype and fill replaced by the stored ones."""
+        aux = self._aux
+        if "values" not in aux:
+            from . import values
+
+            aux["values"] = values.split(self)
+        return aux["values"]
+
     def _nested(self):
         """The outer ShardingCodec of a nested-sharding chain, else None."""
         aux = self._aux
@@ -1272,6 +1284,10 @@ class HipCodecPipeline:
         tensor; item_out_extra (bytes per item) shifts each item's out position,
         so one launch can decode a batch into the slices of a stacked out."""
         torch = _torch()
+        if self._value_split() is not None:
+            from . import values
+
+            values.refuse(self, "prepare_read (planning a read ahead, hipGraph capture)")
         batch = normalize_batch(batch_info)
         if not batch:
             raise ValueError("empty batch")
@@ -1383,6 +1399,11 @@ class HipCodecPipeline:
             batch_info = list(batch_info)
         if type(batch_info) is not BasicBatch and fancy.any_fancy(batch_info):
             return fancy.read(self, batch_info, out, drop_axes)
+        vs = self._value_split()
+        if vs is not None:  # scale_offset / cast_value: stored decode, then the value map (values.py)
+            from . import values
+
+            return values.read(self, vs, batch_info, out, drop_axes)
         batch = normalize_batch(batch_info)
         if not batch:
             return ()
@@ -1622,6 +1643,11 @@ class HipCodecPipeline:
             batch_info = list(batch_info)
         if type(batch_info) is not BasicBatch and fancy.any_fancy(batch_info):  # orthogonal / coordinate / mask
             return fancy.write(self, batch_info, value, drop_axes, partial_encode)
+        vs = self._value_split()
+        if vs is not None:  # scale_offset / cast_value: array-domain merge, value map, stored write
+            from . import values
+
+            return values.write(self, vs, batch_info, value, drop_axes, partial_encode)
         batch = normalize_batch(batch_info)
         if not batch:
             return
@@ -1720,6 +1746,10 @@ class HipCodecPipeline:
         torch = _torch()
         from .buffer import torch_dtype
 
+        if self._value_split() is not None:
+            from . import values
+
+            values.refuse(self, "decode_sync (standalone chunks)")
         items = list(chunk_bytes_and_specs)
         res: list = [None] * len(items)
         groups: dict = {}
@@ -1771,6 +1801,10 @@ class HipCodecPipeline:
         torch = _torch()
         from .writer import _value_tensor
 
+        if self._value_split() is not None:
+            from . import values
+
+            values.refuse(self, "encode_sync (standalone chunks)")
         items = list(chunk_arrays_and_specs)
         res: list = [None] * len(items)
         groups: dict = {}
