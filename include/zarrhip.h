@@ -43,6 +43,11 @@
  *                     MaskIndexer (:1353-1373) for coordinates that are device
  *                     arrays: bounds, chunk of each point, grouping by chunk and
  *                     the pair table zhip_select_copy reads, built on the device.
+ *   zhip_axis_last / zhip_axis_count / zhip_axis_fill
+ *                     IntArrayDimIndexer.__init__, wraparound_indices and
+ *                     boundscheck_indices (indexing.py:732-847) for one axis of an
+ *                     orthogonal selection whose index array is on the device,
+ *                     and the host normaliser's per-dimension keep-last dedupe.
  *   zhip_plan_*       host-side constant tables (no reference counterpart:
  *                     the CRC-combine operators the GPU kernels need).
  *
@@ -726,6 +731,97 @@ int zhip_points_fill(const zhip_points_geom *geom, const int64_t *const *d_coord
  * pairs. */
 int zhip_emulate_points(const zhip_points_geom *geom, const int64_t *const *coords, uint64_t n,
                         uint32_t *counts, uint32_t *err, uint32_t *first, uint32_t *cursor, int64_t *table);
+
+/* ---- device-planned orthogonal axes (orthogonal selections) ----
+ *
+ * For an orthogonal selection (oindex) with an integer index array already on
+ * the device, these plan ONE axis without a host pass over its indices.  They
+ * replace, per index, IntArrayDimIndexer.__init__ with wraparound_indices and
+ * boundscheck_indices (src/zarr/core/indexing.py:732-847: wraparound, bounds
+ * check, the chunk of each index, the argsort that groups indices by chunk,
+ * the per-chunk slices), the host build of the axis' pair table, and -- for a
+ * write with an array value -- the per-dimension keep-last dedupe of the host
+ * normaliser (fancy.normalize(dedupe=True): numpy's a[np.ix_(...)] = v keeps
+ * the last occurrence along each axis).
+ *
+ * An axis has length L, chunk length C and G = ceil(L / C) chunks; x[0 .. n)
+ * are its indices, each in [-L, L).  v = x[k] wrapped, c = v / C, r = v - c C.
+ *
+ *   zhip_axis_last    (keep-last only) last[v] = 1 + the largest k with
+ *                     x[k] == v, by an atomic max onto a zeroed uint32[L]:
+ *                     index k is the WINNER of v iff last[v] == k + 1, whatever
+ *                     the schedule.  Out-of-range indices touch nothing.
+ *   zhip_axis_count   counts[c] += 1, lo_w[c] = max(C - 1 - r), hi_w[c] = max(r)
+ *                     over the counted indices (with `last`: the winners only).
+ *                     All three arrays start zeroed; the chunk's bounds are
+ *                     lo = C - 1 - lo_w[c] and hi = hi_w[c], DEFINED ONLY WHERE
+ *                     counts[c] > 0.  An index out of range ORs geom->err_bit
+ *                     into *d_err and is counted nowhere.
+ *   zhip_axis_fill    every counted index k gets a distinct position p in
+ *                     [0, counts[c]) and its pair is stored at
+ *                     table[table_off + first[c] + p] (first: the exclusive
+ *                     prefix sum of this axis' counts; the order inside a
+ *                     chunk's range is unspecified, every pair carries its own
+ *                     k).  Read (write = 0): A = r * slot_stride, B = k *
+ *                     lin_stride.  Write (write = 1): A = k * lin_stride (0 for
+ *                     a scalar value), B = r * slot_stride.
+ *
+ * The axes of one selection share one error word (err_bit = 1 << selection
+ * axis) and one pair table (table_off = the pairs of the axes before).
+ *
+ * Limits, checked by every entry point (ZHIP_E_UNSUPPORTED past them, nothing
+ * launched; the Python caller tests them first and serves such a selection
+ * with host indices): */
+#define ZHIP_AXIS_MAX_N 0x7fffffffu         /* indices of one axis: n < 2^31 (k + 1 fits a word) */
+#define ZHIP_AXIS_MAX_LEN 0x7fffffffu       /* axis length L < 2^31                              */
+#define ZHIP_AXIS_MAX_GRID (1u << 22)       /* chunks along the axis, G                          */
+#define ZHIP_AXIS_LAST_BYTES (1u << 28)     /* byte budget of one `last` array (256 MiB) ...     */
+#define ZHIP_AXIS_LAST_MAX_LEN (ZHIP_AXIS_LAST_BYTES / 4u)  /* ... so keep-last needs L <= 2^26  */
+#define ZHIP_AXIS_LDS_BINS 4096u            /* G up to this: per-workgroup LDS histogram, one
+                                               global atomic per word of a non-empty bin; longer
+                                               axes: global atomics per index                    */
+#define ZHIP_AXIS_RUN 2048u                 /* indices of one workgroup (256 lanes x 8)          */
+
+typedef struct zhip_axis_geom {
+    uint32_t length;      /* L >= 1                                            */
+    uint32_t chunk;       /* C >= 1                                            */
+    zhip_fdiv div;        /* division by C                                     */
+    uint32_t grid;        /* G = ceil(L / C)                                   */
+    uint32_t write;       /* pair order: 0 read, 1 write                       */
+    uint32_t err_bit;     /* what an out-of-range index ORs into the error word */
+    uint32_t _pad;
+    int64_t slot_stride;  /* byte stride of the axis inside a chunk-shaped slot */
+    int64_t lin_stride;   /* bytes per index on the out (read) / value (write) side */
+    uint64_t table_off;   /* index of the axis' first pair in the shared table */
+} zhip_axis_geom;         /* 56 bytes */
+
+/* d_x: n contiguous int64 indices on the device (8-byte aligned).  n = 0
+ * launches nothing.  All asynchronous on `stream`; afterwards
+ * zhip_last_kernel() is "k_axis_last" / "k_axis_count" / "k_axis_fill".
+ * d_last: geom->length zeroed words (needs L <= ZHIP_AXIS_LAST_MAX_LEN). */
+int zhip_axis_last(const zhip_axis_geom *geom, const int64_t *d_x, uint64_t n, uint32_t *d_last, void *stream);
+/* d_last: NULL, or zhip_axis_last's array for the same indices.  d_counts /
+ * d_lo / d_hi: geom->grid zeroed words each; d_err: one word, zeroed before
+ * the selection's first axis. */
+int zhip_axis_count(const zhip_axis_geom *geom, const int64_t *d_x, uint64_t n, const uint32_t *d_last,
+                    uint32_t *d_counts, uint32_t *d_lo, uint32_t *d_hi, uint32_t *d_err, void *stream);
+/* d_first: geom->grid words, the exclusive prefix sum of zhip_axis_count's
+ * counts for the same indices and the same d_last; d_cursor: geom->grid zeroed
+ * words (each ends equal to its count); d_table: table_pairs pairs (2 int64
+ * each), 16-byte aligned.  A pair whose index would be table_pairs or more is
+ * not written. */
+int zhip_axis_fill(const zhip_axis_geom *geom, const int64_t *d_x, uint64_t n, const uint32_t *d_last,
+                   const uint32_t *d_first, uint32_t *d_cursor, int64_t *d_table, uint64_t table_pairs,
+                   void *stream);
+/* CPU-only test hook: the three steps over host memory with the kernels'
+ * located-index function (one shared host/device function).  Zeroes counts /
+ * lo / hi / cursor (geom->grid words each) and *err; keep_last != 0 zeroes and
+ * fills last (geom->length words) first.  With *err != 0 it stops after the
+ * count (first, cursor and table untouched), else writes first and fills the
+ * table in index order. */
+int zhip_emulate_axis(const zhip_axis_geom *geom, const int64_t *x, uint64_t n, int keep_last, uint32_t *last,
+                      uint32_t *counts, uint32_t *lo, uint32_t *hi, uint32_t *err, uint32_t *first,
+                      uint32_t *cursor, int64_t *table, uint64_t table_pairs);
 
 /* ---- element-wise value codecs: scale_offset and cast_value ----
  *

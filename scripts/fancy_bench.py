@@ -8,7 +8,14 @@ A 256^3 float32 array in 64^3 chunks (bytes + crc32c), device-resident store:
   (iii) the same points as device tensors, planned on the device
        (zarr_hip.points): Array.get end to end, the device-event time of
        count + fill + gather, and the host clock of the planning at a tenth of
-       the points and at all of them.
+       the points and at all of them;
+  (iv) case (i) with the permutation as a device tensor, planned per axis on
+       the device (zarr_hip.axes);
+  (v)  10^6 random row ids with repeats on dimension 0 and 0:4 on the other
+       two, once with host ids and once with device ids.
+       For (iv) and (v): Array.get end to end on both routes of the same run,
+       the device-event time of count + fill + gather, and the host clock of
+       planning + gather at a tenth of the ids and at all of them.
 For (i) and (ii): Array.get(...) end to end (host clock around a call that ends in a
 device synchronise), and the gather launch alone (device events around
 SelectTables.launch: the table upload and k_select_copy) with its bytes per
@@ -44,6 +51,7 @@ def main():
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--chunk", type=int, default=64)
     ap.add_argument("--points", type=int, default=1_000_000)
+    ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--profile", action="store_true")
     args = ap.parse_args()
 
@@ -179,6 +187,63 @@ def main():
             r3[f"plan_and_gather_wall_ms_{args.points // frac}_points"] = {"median": p[0], "min": p[1]}
         res["vindex_points_device"] = r3
     del keep
+    # (iv), (v): orthogonal selections whose index array is a device tensor, planned per axis on the device
+    # (zarr_hip.axes), next to the host-index route of the same run
+    from zarr_hip.axes import DeviceOrthogonalIndexer
+
+    grid = (n // c,) * 3
+
+    def axes_plan_and_gather(dsel, out):
+        """count (+ the one readback) + fill + gather against the decoded scratch."""
+        ix = DeviceOrthogonalIndexer(dsel, shape, chunks)
+        ostr = [int(s) * isz for s in out.stride()]
+        table = ix.build_table(cstr, ostr, False)
+        tabs = fancy.SelectTables(isz, fancy.tensor_extent(scratch), fancy.tensor_extent(out))
+        for it in ix.items():
+            tabs.add_product(it.dims, int(np.ravel_multi_index(it.coords, grid)) * slot_bytes, cstr, ostr)
+        return tabs.launch(scratch, out, dev, table=table), table
+
+    ids = rng.integers(0, n, args.rows)  # with repeats
+    ortho = {"oindex_perm_dim0_device": (perm, slice(None), slice(None)),
+             "oindex_rows_repeats": (ids, slice(0, 4), slice(0, 4))}
+    for name, sel in ortho.items():
+        dsel = (torch.from_numpy(sel[0]).to(dev),) + sel[1:]
+        expect = np.ascontiguousarray(data[sel[0]][:, sel[1], sel[2]])
+        got = arr.get(dsel)
+        if not got.is_cuda or buffer.to_numpy(got, np.float32).tobytes() != expect.tobytes():
+            raise SystemExit(f"fancy_bench: {name} differs from numpy")
+        out = torch.empty(expect.shape, dtype=torch.float32, device=dev)
+        keep = axes_plan_and_gather(dsel, out)
+        sync()
+        if buffer.to_numpy(out, np.float32).tobytes() != expect.tobytes():
+            raise SystemExit(f"fancy_bench: {name}: the timed plan + gather differs from numpy")
+        if args.profile:
+            for _ in range(5):
+                keep = axes_plan_and_gather(dsel, out)
+            sync()
+            continue
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for a, b in ev:
+            a.record()
+            keep = axes_plan_and_gather(dsel, out)
+            b.record()
+        sync()
+        dev_get = wall(lambda: arr.get(dsel), args.reps)
+        host_get = wall(lambda: arr.get(sel), args.reps)
+        r = {"elements": int(expect.size), "ids": int(len(sel[0])),
+             "device_ids_get_ms": {"median": dev_get[0], "min": dev_get[1]},
+             "host_ids_get_ms": {"median": host_get[0], "min": host_get[1]},
+             "count_fill_gather_event_ms": float(np.median([a.elapsed_time(b) for a, b in ev]))}
+        # planning + gather on the host clock at a tenth of the ids and at all of them: per-index host work
+        # would show as a tenfold step
+        for frac in (10, 1):
+            k = len(sel[0]) // frac
+            sub = (dsel[0][:k].contiguous(),) + sel[1:]
+            sub_out = out[:k]
+            p = wall(lambda: axes_plan_and_gather(sub, sub_out), args.reps)
+            r[f"plan_and_gather_wall_ms_{k}_ids"] = {"median": p[0], "min": p[1]}
+        res[name] = r
+        del keep
     if not args.profile:
         b = wall(lambda: arr.get((Ellipsis,)), args.reps)
         res["basic_full_get_ms"] = {"median": b[0], "min": b[1]}

@@ -15,6 +15,7 @@
 #include "../../include/zarrhip.h"
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
+#include "zhip_axis.h"
 #include "zhip_points.h"
 #include "zhip_select.h"
 #include "zhip_values.h"
@@ -1133,6 +1134,108 @@ int zhip_emulate_points(const zhip_points_geom* geom, const int64_t* const* coor
         const uint64_t p = (uint64_t)first[rix] + cursor[rix]++;
         if (p >= n) return set_err(ZHIP_E_BOUNDS, "pair index outside the table");
         points_pair(g, k, off, table[2 * p], table[2 * p + 1]);
+    }
+    return ZHIP_OK;
+}
+
+// ---- zhip_axis_last / zhip_axis_count / zhip_axis_fill: device-planned orthogonal axes (axis.hip) ----
+// The geometry a caller could get wrong, and the limits.
+static int axis_args(const zhip_axis_geom* g, const void* x, uint64_t n, bool keep_last) {
+    if (!g) return set_err(ZHIP_E_INVALID, "null argument");
+    if (g->write > 1) return set_err(ZHIP_E_INVALID, "axis geometry write flag");
+    if (n > ZHIP_AXIS_MAX_N) return set_err(ZHIP_E_UNSUPPORTED, "2^31 or more indices along one axis");
+    if (g->length > ZHIP_AXIS_MAX_LEN) return set_err(ZHIP_E_UNSUPPORTED, "an axis of length 2^31 or more");
+    if (g->length < 1) return set_err(ZHIP_E_INVALID, "axis geometry length");
+    if (g->chunk < 1 || g->chunk > ZHIP_AXIS_MAX_LEN) return set_err(ZHIP_E_INVALID, "axis geometry chunk length");
+    const zhip_fdiv f = make_fdiv(g->chunk);
+    if (f.m != g->div.m || f.s != g->div.s) return set_err(ZHIP_E_INVALID, "axis geometry divisor");
+    if (g->grid != (uint32_t)(((uint64_t)g->length + g->chunk - 1) / g->chunk))
+        return set_err(ZHIP_E_INVALID, "axis geometry grid length");
+    if (g->grid > ZHIP_AXIS_MAX_GRID) return set_err(ZHIP_E_UNSUPPORTED, "more chunks along an axis than ZHIP_AXIS_MAX_GRID");
+    if (keep_last && g->length > ZHIP_AXIS_LAST_MAX_LEN)
+        return set_err(ZHIP_E_UNSUPPORTED, "keep-last on an axis longer than ZHIP_AXIS_LAST_MAX_LEN");
+    if (n && (!x || ((uintptr_t)x & 7))) return set_err(ZHIP_E_INVALID, "index array null or unaligned");
+    return ZHIP_OK;
+}
+
+int zhip_axis_last(const zhip_axis_geom* geom, const int64_t* d_x, uint64_t n, uint32_t* d_last, void* stream) {
+    const int rc = axis_args(geom, d_x, n, true);
+    if (rc != ZHIP_OK) return rc;
+    if (!d_last) return set_err(ZHIP_E_INVALID, "null argument");
+    if (n == 0) return ZHIP_OK;
+    const int e = axis_last_launch(*geom, d_x, (uint32_t)n, d_last, stream);
+    if (e != 0) return set_err(ZHIP_E_HIP, std::string("k_axis_last launch: ") + hipGetErrorString((hipError_t)e));
+    return ZHIP_OK;
+}
+
+int zhip_axis_count(const zhip_axis_geom* geom, const int64_t* d_x, uint64_t n, const uint32_t* d_last,
+                    uint32_t* d_counts, uint32_t* d_lo, uint32_t* d_hi, uint32_t* d_err, void* stream) {
+    const int rc = axis_args(geom, d_x, n, d_last != nullptr);
+    if (rc != ZHIP_OK) return rc;
+    if (!d_counts || !d_lo || !d_hi || !d_err) return set_err(ZHIP_E_INVALID, "null argument");
+    if (n == 0) return ZHIP_OK;
+    const int e = axis_count_launch(*geom, d_x, (uint32_t)n, d_last, d_counts, d_lo, d_hi, d_err, stream);
+    if (e != 0) return set_err(ZHIP_E_HIP, std::string("k_axis_count launch: ") + hipGetErrorString((hipError_t)e));
+    return ZHIP_OK;
+}
+
+int zhip_axis_fill(const zhip_axis_geom* geom, const int64_t* d_x, uint64_t n, const uint32_t* d_last,
+                   const uint32_t* d_first, uint32_t* d_cursor, int64_t* d_table, uint64_t table_pairs, void* stream) {
+    const int rc = axis_args(geom, d_x, n, d_last != nullptr);
+    if (rc != ZHIP_OK) return rc;
+    if (!d_first || !d_cursor || !d_table) return set_err(ZHIP_E_INVALID, "null argument");
+    if ((uintptr_t)d_table & 15) return set_err(ZHIP_E_INVALID, "pair table not 16-byte aligned");
+    if (n == 0) return ZHIP_OK;
+    const int e = axis_fill_launch(*geom, d_x, (uint32_t)n, d_last, d_first, d_cursor, d_table, table_pairs, stream);
+    if (e != 0) return set_err(ZHIP_E_HIP, std::string("k_axis_fill launch: ") + hipGetErrorString((hipError_t)e));
+    return ZHIP_OK;
+}
+
+// The three steps on the host, in index order, with the kernels' axis_locate /
+// axis_pair: keep-last, count, then (no index out of range) the prefix sum and
+// the fill.
+int zhip_emulate_axis(const zhip_axis_geom* geom, const int64_t* x, uint64_t n, int keep_last, uint32_t* last,
+                      uint32_t* counts, uint32_t* lo, uint32_t* hi, uint32_t* err, uint32_t* first, uint32_t* cursor,
+                      int64_t* table, uint64_t table_pairs) {
+    const int rc = axis_args(geom, x, n, keep_last != 0);
+    if (rc != ZHIP_OK) return rc;
+    if (!counts || !lo || !hi || !err || !first || !cursor || (n && !table) || (keep_last && !last))
+        return set_err(ZHIP_E_INVALID, "null argument");
+    const zhip_axis_geom& g = *geom;
+    memset(counts, 0, g.grid * sizeof(uint32_t));
+    memset(lo, 0, g.grid * sizeof(uint32_t));
+    memset(hi, 0, g.grid * sizeof(uint32_t));
+    memset(cursor, 0, g.grid * sizeof(uint32_t));
+    *err = 0;
+    uint32_t v, c, r;
+    if (keep_last) {
+        memset(last, 0, (size_t)g.length * sizeof(uint32_t));
+        for (uint64_t k = 0; k < n; ++k)
+            if (axis_locate(g, x[k], v, c, r) && last[v] < (uint32_t)k + 1u) last[v] = (uint32_t)k + 1u;
+    }
+    for (uint64_t k = 0; k < n; ++k) {
+        if (!axis_locate(g, x[k], v, c, r)) {
+            *err |= g.err_bit;
+            continue;
+        }
+        if (keep_last && last[v] != (uint32_t)k + 1u) continue;
+        counts[c] += 1;
+        const uint32_t lw = axis_lo_word(g, r);
+        if (lw > lo[c]) lo[c] = lw;
+        if (r > hi[c]) hi[c] = r;
+    }
+    if (*err) return ZHIP_OK;
+    uint32_t at = 0;
+    for (uint32_t b = 0; b < g.grid; ++b) {
+        first[b] = at;
+        at += counts[b];
+    }
+    for (uint64_t k = 0; k < n; ++k) {
+        if (!axis_locate(g, x[k], v, c, r)) continue;
+        if (keep_last && last[v] != (uint32_t)k + 1u) continue;
+        const uint64_t p = g.table_off + first[c] + cursor[c]++;
+        if (p >= table_pairs) return set_err(ZHIP_E_BOUNDS, "pair index outside the table");
+        axis_pair(g, k, r, table[2 * p], table[2 * p + 1]);
     }
     return ZHIP_OK;
 }

@@ -213,6 +213,19 @@ POINTS_GEOM_DT = np.dtype([("ndim", "<i4"), ("write", "<u4"), ("pair_stride", "<
                            ("slot_stride", "<i8", (MAX_DIMS,))])
 assert POINTS_GEOM_DT.itemsize == 240
 
+# zhip_axis_geom and the limits of zhip_axis_last / zhip_axis_count / zhip_axis_fill (include/zarrhip.h)
+AXIS_MAX_N = 0x7FFFFFFF
+AXIS_MAX_LEN = 0x7FFFFFFF
+AXIS_MAX_GRID = 1 << 22
+AXIS_LAST_BYTES = 1 << 28
+AXIS_LAST_MAX_LEN = AXIS_LAST_BYTES // 4
+AXIS_LDS_BINS = 4096
+AXIS_RUN = 2048
+AXIS_GEOM_DT = np.dtype([("length", "<u4"), ("chunk", "<u4"), ("div", "<u4", (2,)), ("grid", "<u4"), ("write", "<u4"),
+                         ("err_bit", "<u4"), ("_pad", "<u4"), ("slot_stride", "<i8"), ("lin_stride", "<i8"),
+                         ("table_off", "<u8")])
+assert AXIS_GEOM_DT.itemsize == 56
+
 
 class NativeError(RuntimeError):
     pass
@@ -352,6 +365,14 @@ def lib():
     L.zhip_points_fill.restype = ctypes.c_int
     L.zhip_emulate_points.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp]
     L.zhip_emulate_points.restype = ctypes.c_int
+    L.zhip_axis_last.argtypes = [vp, vp, u64, vp, vp]
+    L.zhip_axis_last.restype = ctypes.c_int
+    L.zhip_axis_count.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp]
+    L.zhip_axis_count.restype = ctypes.c_int
+    L.zhip_axis_fill.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, vp]
+    L.zhip_axis_fill.restype = ctypes.c_int
+    L.zhip_emulate_axis.argtypes = [vp, vp, u64, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, u64]
+    L.zhip_emulate_axis.restype = ctypes.c_int
     if L.zhip_abi_version() != 1:
         raise NativeError("libzarrhip ABI version mismatch")
     if L.zhip_tuning_build() and not _override_allowed():

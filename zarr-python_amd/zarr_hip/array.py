@@ -18,7 +18,7 @@ from typing import Any
 
 import numpy as np
 
-from . import buffer, points
+from . import axes, buffer, points
 from .codecs import BytesCodec, Crc32cCodec, ShardingCodec, parse_codecs
 from .grid import ChunkGrid
 from .indexing import (CoordinateIndexer, MaskIndexer, OrthogonalIndexer, basic_projections, chunk_batch,
@@ -285,6 +285,8 @@ class Array:
         orthogonal, coordinate and mask selections too: dispatched as
         __getitem__ does)."""
         kind = self._dispatch(selection)
+        if kind == "device-oindex":
+            return self._get_axes(selection, out, device)
         if kind is not None:
             return self._get_fancy(self._indexer(kind, selection), out, device)
         batch, out_shape = self.batch_info(selection)
@@ -309,6 +311,8 @@ class Array:
         device and copy the result back once."""
         st = self.store_path.store
         kind = self._dispatch(selection)
+        if kind == "device-oindex":
+            return buffer.to_numpy(self._get_axes(selection), self.metadata.dtype)
         if kind == "device":  # indices on the device: planned there; the result is still a host array
             return buffer.to_numpy(self._get_fancy(self._indexer(kind, selection)), self.metadata.dtype)
         if kind is not None:
@@ -331,6 +335,8 @@ class Array:
         """Array._set_selection (array.py:5563-5675): value may be a device
         tensor, a numpy array or a scalar."""
         kind = self._dispatch(selection)
+        if kind == "device-oindex":
+            return self._set_axes(selection, value)
         if kind is not None:
             return self._set_fancy(self._indexer(kind, selection), value)
         batch, out_shape = self.batch_info(selection)
@@ -351,13 +357,19 @@ class Array:
     # ------------------------------- orthogonal, coordinate and mask selections
     def _dispatch(self, selection):
         """Array.__getitem__'s dispatch (array.py:2635-2641, indexing.py:270-331):
-        "vindex", "oindex", or None for a basic selection; "device" for a
-        selection that holds device tensors (points.py)."""
+        "vindex", "oindex", or None for a basic selection; for a selection
+        that holds device tensors "device" (coordinates or a mask, points.py)
+        or "device-oindex" (orthogonal, axes.py)."""
         if _selection_key(selection) is not None:
             return None
-        if points.has_device_index(selection):
-            return "device"
         nd = len(self.metadata.shape)
+        if points.has_device_index(selection):
+            # zarr's order with a device tensor counting as an array: pure fancy
+            # first, then pure orthogonal (axes.py); what neither rule admits
+            # goes to the coordinate indexer, which raises for it
+            if not axes.is_pure_fancy(selection, nd) and axes.is_pure_orthogonal(selection, nd):
+                return "device-oindex"
+            return "device"
         if is_pure_fancy_indexing(selection, nd):
             return "vindex"
         if is_pure_orthogonal_indexing(selection, nd):
@@ -489,6 +501,79 @@ class Array:
             fancy.write_points(self.codec_pipeline, getters, self.spec, ix, value,
                                distinct=isinstance(ix, points.DeviceMaskIndexer))
 
+    # --- orthogonal selections whose index arrays are device tensors (axes.py)
+    def _axes_indexer(self, selection, keep_last: bool):
+        """DeviceOrthogonalIndexer; past the device route's limits the host
+        OrthogonalIndexer over a host copy of the indices."""
+        md = self.metadata
+        chunks = self._regular_chunks()
+        try:
+            return axes.DeviceOrthogonalIndexer(selection, md.shape, chunks, keep_last=keep_last)
+        except points.PointsLimit:
+            return OrthogonalIndexer(points.to_host(selection), md.shape, chunks)
+
+    def _axes_getters(self, ix) -> list:
+        store = self.store_path.store
+        return [StorePath(store, self._key(it.coords)) for it in ix.items()]
+
+    def _get_axes(self, selection, out=None, device=None):
+        """A device tensor of the selection's shape; with `out` (a device
+        tensor, views included, or a host array of that shape): out, filled."""
+        from . import fancy
+        from .interop import device_tensor, host_array
+
+        ix = self._axes_indexer(selection, keep_last=False)
+        if not isinstance(ix, axes.DeviceOrthogonalIndexer):
+            return self._get_fancy(ix, out, device)
+        dev = self._run_device(ix, device)
+        dt = self.metadata.dtype
+        target = None
+        if out is not None:
+            target = device_tensor(out)
+            if target is None:
+                target = host_array(out)
+                if target is None:
+                    raise TypeError(f"cannot decode into a {type(out).__name__}")
+            if tuple(target.shape) != tuple(ix.shape):
+                raise ValueError(f"out of shape {tuple(target.shape)} for a selection of shape {tuple(ix.shape)}")
+        direct = target is not None and hasattr(target, "is_cuda") and target.device == dev
+        dev_out = target if direct else buffer.empty(ix.shape, dt, dev, self.config.order)
+        getters = self._axes_getters(ix)
+        if getters:
+            results = fancy.read_axes(self.codec_pipeline, getters, self.spec, ix, dev_out)
+            self._check_missing([(g,) for g in getters], results)
+        if target is None:
+            return dev_out
+        if not direct:
+            if hasattr(target, "is_cuda"):
+                target.copy_(dev_out)
+            else:
+                buffer.copy_to_host(dev_out, target)
+        return out
+
+    def _set_axes(self, selection, value) -> None:
+        import torch
+
+        from . import fancy
+
+        scalar = value.dim() == 0 if isinstance(value, torch.Tensor) else np.ndim(value) == 0
+        # an array value: the last occurrence of a repeated index along an axis wins
+        ix = self._axes_indexer(selection, keep_last=not scalar)
+        if not isinstance(ix, axes.DeviceOrthogonalIndexer):
+            return self._set_fancy(ix, value)
+        self._run_device(ix)
+        if isinstance(value, torch.Tensor):
+            if value.dim() > 0 and tuple(value.shape) != tuple(ix.shape):
+                value = value.broadcast_to(ix.shape)
+        else:
+            a = np.asarray(value, dtype=self.metadata.dtype)
+            if a.shape not in ((), tuple(ix.shape)):
+                a = np.broadcast_to(a, ix.shape)
+            value = a
+        getters = self._axes_getters(ix)
+        if getters:
+            fancy.write_axes(self.codec_pipeline, getters, self.spec, ix, value)
+
     def _get_fancy(self, indexer, out=None, device=None):
         import torch
 
@@ -535,11 +620,16 @@ class Array:
 
     def get_orthogonal_selection(self, selection, out=None):
         """Array.get_orthogonal_selection: a host result (a device tensor: oindex
-        through get(), or pass a device `out`)."""
+        through get(), or pass a device `out`).  Index arrays given as device
+        tensors are planned on the device and give a device tensor (axes.py)."""
+        if points.has_device_index(selection):
+            return self._get_axes(selection, out)
         ix = OrthogonalIndexer(selection, self.metadata.shape, self._regular_chunks())
         return self._get_fancy_host(ix) if out is None else self._get_fancy(ix, out)
 
     def set_orthogonal_selection(self, selection, value) -> None:
+        if points.has_device_index(selection):
+            return self._set_axes(selection, value)
         self._set_fancy(OrthogonalIndexer(selection, self.metadata.shape, self._regular_chunks()), value)
 
     def get_coordinate_selection(self, selection, out=None):

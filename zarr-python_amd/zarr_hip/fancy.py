@@ -30,6 +30,10 @@ that groups indices by chunk is not stable (indexing.py:803, 1299).
 Coordinate and mask selections whose indices are device tensors skip the host
 normaliser: read_points / write_points run the same slots, scratch budget and
 routes over a pair table that k_points_fill built on the device (points.py).
+Orthogonal selections whose index arrays are device tensors do the same one
+axis at a time: read_axes / write_axes run items that are products of affine
+dimensions and ranges of a table k_axis_fill built (axes.py), each decoded in
+the box the count kernel's per-chunk bounds give.
 """
 
 from __future__ import annotations
@@ -115,6 +119,40 @@ class Normalized:
     dims: list           # [PDim], in element order (last fastest)
     box: list            # per chunk axis (lo, hi): min .. max + 1 of the selected indices
     total: int
+
+
+@dataclass
+class AffineDim:
+    """A slice or an integer of one item: chunk indices start + k step; out
+    indices out_start + k along out_axis (None: an integer, dropped)."""
+
+    count: int
+    start: int
+    step: int
+    out_axis: int | None
+    out_start: int
+
+    @property
+    def box(self) -> tuple:
+        return self.start, self.start + (self.count - 1) * self.step + 1
+
+
+@dataclass
+class TableDim:
+    """The indices of one chunk along a tensor axis: pairs [table_off,
+    table_off + count) of the DEVICE table; their in-chunk indices lie in
+    [lo, hi] and their positions in the index tensor in [0, n)."""
+
+    count: int
+    table_off: int
+    lo: int
+    hi: int
+    n: int
+    out_axis: int
+
+    @property
+    def box(self) -> tuple:
+        return self.lo, self.hi + 1
 
 
 def _arr(x):
@@ -430,6 +468,70 @@ class SelectTables:
         rec["a_base"], rec["b_base"] = lo[za], lo[zb]
         rec["ndim"] = 1
         rec["total"] = count
+        self.items.append(rec)
+
+    def add_product(self, dims, slot_base: int, chunk_strides, lin_strides, write: bool = False) -> None:
+        """One touched chunk of a device-planned orthogonal selection
+        (axes.py): a product of dimensions that are each affine on both sides
+        (AffineDim: a slice or an integer) or a range of the DEVICE table
+        given to launch() (TableDim, pairs built by zhip_axis_fill).
+        chunk_strides: byte strides of the slot at slot_base per array
+        dimension; lin_strides: byte strides of out / value per selected
+        dimension (None: a scalar value).  A table dimension's slot-side
+        entries lie in [lo, hi] * stride -- the bounds read back from the
+        count -- and the other side's in [0, (n - 1) * lin stride], so the
+        item's extreme offsets are checked from those ends."""
+        base = [int(slot_base), 0]
+        lo = [int(slot_base), 0]
+        hi = [int(slot_base), 0]
+        rec = np.zeros((), N.SELECT_ITEM_DT)
+        za, zb = (1, 0) if write else (0, 1)
+        nd, total = 0, 1
+        for d, D in enumerate(dims):
+            cst = int(chunk_strides[d])
+            ost = 0 if (lin_strides is None or D.out_axis is None) else int(lin_strides[D.out_axis])
+            if D.count < 1:
+                return
+            total *= D.count
+            if isinstance(D, TableDim):
+                ends = [(D.lo * cst, D.hi * cst), (0, (D.n - 1) * ost)]
+                if not (0 <= D.lo <= D.hi and 1 <= D.count <= D.n):
+                    raise IndexError(f"a table dimension with bounds {D.lo} .. {D.hi} and {D.count} of {D.n} indices")
+            else:
+                start = [D.start * cst, D.out_start * ost]
+                step = [D.step * cst, ost]
+                ends = [(start[z], start[z] + (D.count - 1) * step[z]) for z in (0, 1)]
+            for z in (0, 1):
+                lo[z] += min(ends[z])
+                hi[z] += max(ends[z])
+            if D.count == 1 and not isinstance(D, TableDim):  # folded into the bases: no division for it
+                for z in (0, 1):
+                    base[z] += start[z]
+                continue
+            if nd >= N.MAX_DIMS:
+                raise NotImplementedError(f"a selection of more than {N.MAX_DIMS} product dimensions")
+            R = rec["dims"][nd]
+            R["count"] = D.count
+            R["div"] = N.fdiv(D.count)
+            if isinstance(D, TableDim):
+                R["table"] = 1
+                R["table_off"] = D.table_off
+            else:
+                R["a0"], R["sa"], R["b0"], R["sb"] = start[za], step[za], start[zb], step[zb]
+            nd += 1
+        if total >= 1 << 31:
+            raise NotImplementedError("a selection of 2**31 or more elements of one chunk")
+        if nd == 0:  # a single element
+            rec["dims"][0]["count"] = 1
+            rec["dims"][0]["div"] = N.fdiv(1)
+            nd = 1
+        for z, size, name in ((za, self.a_size, "source"), (zb, self.b_size, "destination")):
+            if lo[z] < 0 or hi[z] + self.itemsize > size:
+                raise IndexError(f"selection reaches outside its {name} buffer (bytes {lo[z]} .. "
+                                 f"{hi[z] + self.itemsize} of {size})")
+        rec["a_base"], rec["b_base"] = base[za], base[zb]
+        rec["ndim"] = nd
+        rec["total"] = total
         self.items.append(rec)
 
     def finish(self):
@@ -808,6 +910,141 @@ def write_points(pipe, getters, spec, ix, value, distinct: bool, partial_encode:
                 wbatch.append((getters[k], spec, csel, osel, True))
                 tabs.add_points(int(ix.counts[k]), int(ix.first[k]), j * slot_bytes, slot_bytes, (n - 1) * vstride,
                                 write=True)
+            if direct:
+                p = pipe.prepare_read(rbatch, scratch)
+                p.launch()
+                up = tabs.launch(v, scratch, device, table=table)
+                p.results_fast()  # a checksum mismatch raises here: nothing stored yet
+                del up
+            else:
+                pipe.read_sync(rbatch, scratch)
+                tabs.launch(v, scratch, device, table=table)
+            pipe._write_sync(wbatch, scratch, (), partial_encode)
+        del table
+
+
+# ------------------------------------- device-planned orthogonal selections
+def _axes_setup(pipe, spec, ix, n_getters: int):
+    if spec.ndim == 0:
+        raise NotImplementedError("a non-basic selection of a 0-dimensional chunk")
+    if tuple(int(s) for s in spec.shape) != tuple(ix.chunk_shape):
+        raise ValueError("the indexer's chunk shape is not the spec's")
+    items = ix.items()
+    if n_getters != len(items):
+        raise ValueError(f"{n_getters} byte getters for {len(items)} touched chunks")
+    return items
+
+
+def read_axes(pipe, getters, spec, ix, dev_out) -> tuple:
+    """An orthogonal read planned on the device (axes.py): getters[i] is the
+    chunk of ix.items()[i]; dev_out a device tensor of shape ix.shape (any
+    strides) on the indexer's device.  Each touched chunk is one item whose
+    box is the product of its per-axis ranges -- the minimum .. maximum
+    in-chunk index read back for tensor axes -- decoded into its slot at its
+    own chunk coordinates (only the touched inner chunks of a shard); every
+    tensor axis' pairs sit in one table built once by k_axis_fill, the
+    sub-batches differ only in their items.  Slots, scratch budget, the direct
+    and composed routes and the single result readback are read()'s."""
+    from .buffer import torch_dtype
+    from .pipeline import ProgramGroup, _torch
+
+    torch = _torch()
+    items = _axes_setup(pipe, spec, ix, len(getters))
+    device = dev_out.device
+    if device != ix.device:
+        raise ValueError(f"the indices are on {ix.device}, the read runs on {device}")
+    itemsize = dev_out.element_size()
+    if np.dtype(spec.dtype).itemsize != itemsize:
+        raise TypeError("out dtype itemsize does not match the array dtype")
+    if tuple(dev_out.shape) != tuple(ix.shape):
+        raise ValueError(f"out of shape {tuple(dev_out.shape)} for a selection of shape {tuple(ix.shape)}")
+    if not items:
+        return ()
+    ostr = [int(s) * itemsize for s in dev_out.stride()]
+    results: list = [None] * len(getters)
+    direct = _direct(pipe)
+    s0 = spec.shape[0]
+    cstr = _scratch_strides(spec, itemsize)
+    slot_bytes = cstr[0] * s0
+    per = _slots(spec, len(getters))
+    progs, groups, keep = [], [], []
+    with torch.cuda.device(device):
+        scratch = torch.empty((per * s0,) + tuple(spec.shape[1:]), dtype=torch_dtype(spec.dtype), device=device)
+        table = ix.build_table(cstr, ostr, False)
+        for at in range(0, len(getters), per):
+            idx = list(range(at, min(at + per, len(getters))))
+            tabs = SelectTables(itemsize, tensor_extent(scratch), tensor_extent(dev_out))
+            boxes = []
+            for j, k in enumerate(idx):
+                it = items[k]
+                boxes.append((getters[k], spec, tuple(slice(lo, hi) for lo, hi in it.box), _slot_sel(it.box, j, s0),
+                              False))
+                tabs.add_product(it.dims, j * slot_bytes, cstr, ostr)
+            if direct:
+                p = pipe.prepare_read(boxes, scratch)
+                p.launch()
+                progs.append(p)
+                groups.append(idx)
+            else:
+                for i, r in zip(idx, pipe.read_sync(boxes, scratch)):
+                    results[i] = r
+            keep.append(tabs.launch(scratch, dev_out, device, table=table))
+        if progs:  # ONE readback of every launch's error and verdict words, after the last gather
+            for i, r in enumerate(ProgramGroup(progs, groups, len(getters)).results_fast()):
+                if r is not None:
+                    results[i] = r
+    del keep, table
+    return tuple(results)
+
+
+def write_axes(pipe, getters, spec, ix, value, partial_encode: bool = True) -> None:
+    """An orthogonal write planned on the device: the box of every touched
+    chunk (_write_box's rule on the narrowed box) is decoded into its slot (a
+    missing chunk gives fill, a CRC mismatch raises before anything of its
+    sub-batch is stored), k_select_copy scatters value into the slots, and the
+    boxes are written back through the basic write path.  value: a scalar
+    (equal values racing to one address), or an array of shape ix.shape with
+    an indexer built with keep_last (only the last occurrence of a repeated
+    index along an axis has a pair)."""
+    from .buffer import torch_dtype
+    from .pipeline import _resolve_value, _torch
+    from .writer import _value_tensor
+
+    torch = _torch()
+    items = _axes_setup(pipe, spec, ix, len(getters))
+    value = _resolve_value(value)
+    scalar = (isinstance(value, torch.Tensor) and value.dim() == 0) or \
+        (not isinstance(value, torch.Tensor) and np.ndim(value) == 0)
+    if not scalar and not ix.keep_last:
+        raise ValueError("an array value through a device-planned orthogonal selection needs keep_last planning")
+    if not items:
+        return
+    device = ix.device
+    itemsize = np.dtype(spec.dtype).itemsize
+    with torch.cuda.device(device):
+        v = _value_tensor(value, spec.dtype, device)
+        v = v.reshape(1) if scalar else v
+        if not scalar and tuple(v.shape) != tuple(ix.shape):
+            raise ValueError(f"value of shape {tuple(v.shape)} for a selection of shape {tuple(ix.shape)}")
+        vstr = None if scalar else [int(s) * itemsize for s in v.stride()]
+        s0 = spec.shape[0]
+        cstr = _scratch_strides(spec, itemsize)
+        slot_bytes = cstr[0] * s0
+        per = _slots(spec, len(getters))
+        direct = _direct(pipe)
+        scratch = torch.empty((per * s0,) + tuple(spec.shape[1:]), dtype=torch_dtype(spec.dtype), device=device)
+        table = ix.build_table(cstr, vstr, True)
+        for at in range(0, len(getters), per):
+            rbatch, wbatch = [], []
+            tabs = SelectTables(itemsize, tensor_extent(v), tensor_extent(scratch))
+            for j, k in enumerate(range(at, min(at + per, len(getters)))):
+                it = items[k]
+                box, complete = _write_box(pipe, spec, Normalized([], it.box, it.total))
+                csel = tuple(slice(lo, hi) for lo, hi in box)
+                osel = _slot_sel(box, j, s0)
+                rbatch.append((getters[k], spec, csel, osel, False))
+                wbatch.append((getters[k], spec, csel, osel, complete))
+                tabs.add_product(it.dims, j * slot_bytes, cstr, vstr, write=True)
             if direct:
                 p = pipe.prepare_read(rbatch, scratch)
                 p.launch()
