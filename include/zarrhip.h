@@ -92,6 +92,12 @@ extern "C" {
 #define ZHIP_LF_INDEX_START 8u    /* sharding index_location == "start"             */
 #define ZHIP_LF_NO_WRITE 16u      /* verify only (shard index CRC)                  */
 #define ZHIP_LF_FLOAT 32u         /* items are IEEE floats (NaN-aware fill equality) */
+#define ZHIP_LF_COMPLEX 64u       /* 8-byte items of two float32 (complex64): under  *
+                                   * ZHIP_LF_SWAP each 4-byte half is reversed in    *
+                                   * place; fill equality is np.array_equal's with   *
+                                   * equal_nan (components as IEEE values, +-0 equal; *
+                                   * any NaN item equals a fill with a NaN component) *
+                                   * -- itemsize 8, never with ZHIP_LF_FLOAT          */
 
 /* chunk flags (zhip_chunk.flags) */
 #define ZHIP_CF_MISSING 1u        /* store returned None: scatter fill value        */
@@ -950,6 +956,15 @@ int zhip_emulate_value_map(const zhip_value_op *op, const zhip_value_item *items
                            const uint32_t *tile_prefix, uint32_t n_tiles, const zhip_status *status,
                            uint32_t n_status, const void *a, uint64_t a_size, void *b, uint64_t b_size,
                            uint32_t *err, uint32_t *nonempty);
+
+/* CPU-only test hook: the encode kernels' "item equals the fill" rule
+ * (NDBuffer.all_equal, src/zarr/core/buffer/core.py:534-558; one header shared
+ * with the kernels) over n_items native-order items of `itemsize` bytes:
+ * eq[i] = 1 when item i equals the fill.  lflags: ZHIP_LF_FLOAT or
+ * ZHIP_LF_COMPLEX select the float / complex64 rule, anything else compares
+ * bits.  *fill_nan (may be null) gets the launch's "the fill is a NaN" word. */
+int zhip_emulate_fill_eq(uint32_t itemsize, uint32_t lflags, const void *fill, const void *items,
+                         uint64_t n_items, uint8_t *eq, uint32_t *fill_nan);
 
 /* Host CRC-32C (reflected 0x82F63B78, init / xorout 0xFFFFFFFF) of nbytes at
  * data: the host stage of a chain, where the bytes never reach the GPU -- a

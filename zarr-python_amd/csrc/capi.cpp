@@ -16,6 +16,7 @@
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
 #include "zhip_axis.h"
+#include "zhip_fill_eq.h"
 #include "zhip_points.h"
 #include "zhip_select.h"
 #include "zhip_values.h"
@@ -131,6 +132,8 @@ int zhip_plan_create(const zhip_layout* layout, zhip_plan** out) {
     if (L.ndim < 1 || L.ndim > ZHIP_MAX_DIMS) return set_err(ZHIP_E_UNSUPPORTED, "ndim must be 1..8");
     if (!(L.itemsize == 1 || L.itemsize == 2 || L.itemsize == 4 || L.itemsize == 8))
         return set_err(ZHIP_E_UNSUPPORTED, "itemsize must be 1, 2, 4 or 8");
+    if ((L.flags & ZHIP_LF_COMPLEX) && ((L.flags & ZHIP_LF_FLOAT) || L.itemsize != 8))
+        return set_err(ZHIP_E_INVALID, "ZHIP_LF_COMPLEX is an 8-byte item of two float32, without ZHIP_LF_FLOAT");
     uint64_t n = (uint64_t)L.itemsize;
     for (int d = 0; d < L.ndim; ++d) {
         if (L.shape[d] < 0) return set_err(ZHIP_E_INVALID, "negative shape");
@@ -806,13 +809,8 @@ int zhip_encode_mapped(const zhip_plan* plan, const void* arr, void* dst, const 
     p.seg = plan->seg;
     p.E = plan->E;
     std::memcpy(p.fill, plan->fill, sizeof(p.fill));
-    p.fill_nan = 0;
-    if (L.flags & ZHIP_LF_FLOAT) {
-        if (L.itemsize == 4) p.fill_nan = (p.fill[0] & 0x7FFFFFFFu) > 0x7F800000u;
-        else if (L.itemsize == 2) p.fill_nan = (p.fill[0] & 0x7FFFu) > 0x7C00u;
-        else if (L.itemsize == 8)
-            p.fill_nan = ((((uint64_t)p.fill[1] << 32) | p.fill[0]) & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull;
-    }
+    p.fill_nan = fill_is_nan(L.itemsize, (L.flags & ZHIP_LF_FLOAT) != 0, (L.flags & ZHIP_LF_COMPLEX) != 0, p.fill[0],
+                             p.fill[1]) ? 1u : 0u;
     p.fast = (encode_flags & ZHIP_DF_FAST_ROWS) ? 1u : 0u;
     p.tune = g_tune_bits;
     p.rowmap = nullptr;
@@ -1032,6 +1030,40 @@ int zhip_value_map(const zhip_value_op* op, const zhip_value_item* d_items, uint
     const int e = value_launch(*op, d_items, n_items, d_tile_prefix, n_tiles, d_status, a, a_size, b, b_size,
                                d_err, d_nonempty, stream);
     if (e != 0) return set_err(ZHIP_E_HIP, std::string("k_value_map launch: ") + hipGetErrorString((hipError_t)e));
+    return ZHIP_OK;
+}
+
+int zhip_emulate_fill_eq(uint32_t itemsize, uint32_t lflags, const void* fill, const void* items, uint64_t n_items,
+                         uint8_t* eq, uint32_t* fill_nan) {
+    if (!fill || (n_items && (!items || !eq))) return set_err(ZHIP_E_INVALID, "null argument");
+    if (!(itemsize == 1 || itemsize == 2 || itemsize == 4 || itemsize == 8))
+        return set_err(ZHIP_E_UNSUPPORTED, "itemsize must be 1, 2, 4 or 8");
+    const bool cplx = (lflags & ZHIP_LF_COMPLEX) != 0, flt = (lflags & ZHIP_LF_FLOAT) != 0;
+    if (cplx && (flt || itemsize != 8))
+        return set_err(ZHIP_E_INVALID, "ZHIP_LF_COMPLEX is an 8-byte item of two float32, without ZHIP_LF_FLOAT");
+    // the fill replicated to 16 bytes, as zhip_plan_create keeps it
+    uint8_t f16[16];
+    for (int i = 0; i < 16; ++i) f16[i] = static_cast<const uint8_t*>(fill)[i % itemsize];
+    uint32_t f[4];
+    std::memcpy(f, f16, 16);
+    const uint32_t fnan = fill_is_nan((int)itemsize, flt, cplx, f[0], f[1]) ? 1u : 0u;
+    if (fill_nan) *fill_nan = fnan;
+    const uint8_t* src = static_cast<const uint8_t*>(items);
+    for (uint64_t i = 0; i < n_items; ++i) {
+        // item i as the first (and only valid) item of a 16-byte block, as the kernels' tail blocks have it
+        uint32_t v[4] = {0u, 0u, 0u, 0u};
+        std::memcpy(v, src + i * itemsize, itemsize);
+        bool e;
+        switch (itemsize) {
+            case 1: e = block_eq_fill_bits<1>(v[0], v[1], v[2], v[3], 1u, f, fnan); break;
+            case 2: e = block_eq_fill_bits<2>(v[0], v[1], v[2], v[3], 2u, f, fnan); break;
+            case 4: e = block_eq_fill_bits<4>(v[0], v[1], v[2], v[3], 4u, f, fnan); break;
+            default:
+                e = cplx ? block_eq_fill_bits<8, true>(v[0], v[1], v[2], v[3], 8u, f, fnan)
+                         : block_eq_fill_bits<8>(v[0], v[1], v[2], v[3], 8u, f, fnan);
+        }
+        eq[i] = e ? 1u : 0u;
+    }
     return ZHIP_OK;
 }
 

@@ -49,7 +49,7 @@ int g_tune_max_grid = 0;
 // contiguous, balanced range of them.  Consecutive units of one chunk then
 // continue the same per-thread Horner chain (stride 4096 B), so a workgroup
 // reduces, shifts and publishes once per (chunk, run), not once per unit.
-template <bool CRC, bool WRITE, bool FAST, int ITEM, bool SWAP, int K = 8>
+template <bool CRC, bool WRITE, bool FAST, int ITEM, int SWAP, int K = 8>
 __global__ __launch_bounds__(kThreads) void k_decode(const DecodeParams p) {
     __shared__ uint32_t s_tab[CRC ? 16 * 256 : 1];
     __shared__ uint32_t s_red[2][kThreads / 64];
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void k_decode(const DecodeParams p) {
 // a Horner chain with stride-specific tables; per-thread / per-tile shift
 // constants (host-built) bring every tile's contribution to the chunk reference.
 // ---------------------------------------------------------------------------
-template <bool CRC, int ITEM, bool SWAP>
+template <bool CRC, int ITEM, int SWAP>
 __global__ __launch_bounds__(kThreads) void k_decode_tile(const DecodeParams p) {
     constexpr int kPitch = ITEM == 8 ? 264 : 260;  // bytes per LDS tile row (2-way read conflicts)
     constexpr int kPasses = kTileRows / 16;
@@ -451,13 +451,13 @@ __global__ __launch_bounds__(kThreads) void k_decode_tile(const DecodeParams p) 
 }
 
 template <bool CRC, bool WRITE, bool FAST, int K>
-static KernelFn pick_item(int item, bool swap) {
+static KernelFn pick_item(int item, int swap) {
     return for_item(item, swap, [](auto t) -> KernelFn {
         return k_decode<CRC, WRITE, FAST, decltype(t)::item, decltype(t)::swap, K>;
     });
 }
 
-KernelFn select_decode_kernel(bool crc, bool write, bool fast, int item, bool swap, int k) {
+KernelFn select_decode_kernel(bool crc, bool write, bool fast, int item, int swap, int k) {
     if (!write) {
         if (!crc) return nullptr;
         return k == 4 ? k_decode<true, false, false, 1, false, 4>
@@ -472,7 +472,7 @@ KernelFn select_decode_kernel(bool crc, bool write, bool fast, int item, bool sw
     return fast ? pick_item<false, true, true, 8>(item, swap) : pick_item<false, true, false, 8>(item, swap);
 }
 
-static KernelFn select_tile_kernel(bool crc, int item, bool swap) {
+static KernelFn select_tile_kernel(bool crc, int item, int swap) {
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);
         return crc ? k_decode_tile<true, T::item, T::swap> : k_decode_tile<false, T::item, T::swap>;
@@ -520,7 +520,8 @@ struct Launch {
     // the look-back finalizer (publish_lb) waits only while fewer chunks than
     // CUs are in the launch
     bool lb_ok;
-    bool crc, swap;
+    bool crc;
+    int swap;  // item_mode(): ZHIP_LF_SWAP | 2 * ZHIP_LF_COMPLEX
     int item;
 };
 
@@ -860,7 +861,7 @@ static Launch make_launch(const DecodeParams& p, hipStream_t stream, int max_gri
     const bool crc = (p.lflags & ZHIP_LF_CRC) != 0;
     const bool lb_ok = p.n_chunks < (uint32_t)(max_grid / 8);  // max_grid arrives as CUs * 8
     if (g_tune_max_grid > 0) max_grid = g_tune_max_grid;
-    return {p, stream, max_grid, ZHIP_TUNING ? p.tune : 0u, lb_ok, crc, (p.lflags & ZHIP_LF_SWAP) != 0,
+    return {p, stream, max_grid, ZHIP_TUNING ? p.tune : 0u, lb_ok, crc, item_mode(p.lflags, (int)p.g.itemsize),
             p.g.itemsize};
 }
 

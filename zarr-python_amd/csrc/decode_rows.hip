@@ -221,7 +221,7 @@ __device__ __forceinline__ void retire_uniform(const DecodeParams& p, PendingU& 
 
 }  // namespace
 
-template <bool CRC, int ITEM, bool SWAP, int K = 8>
+template <bool CRC, int ITEM, int SWAP, int K = 8>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_decode_rows(const DecodeParams p) {
     __shared__ uint32_t s_tab[CRC ? 16 * 256 : 1];
     __shared__ uint32_t s_mul[CRC ? 16 * kThreads : 1];
@@ -520,7 +520,7 @@ __device__ __forceinline__ RowSteps load_row_steps(const DecodeParams& p, const 
 // Stores of one unit; with `crc` the Horner step of each block follows its
 // store (the lookups spread over the data's arrival instead of trailing it).
 // Destinations come from the row map: no per-step address arithmetic.
-template <int ITEM, bool SWAP, int K, bool SKIP = false>
+template <int ITEM, int SWAP, int K, bool SKIP = false>
 __device__ __forceinline__ void store_unit_rows(const DecodeParams& p, const Unit& U, const RowSteps& m, bool live,
                                                 uint32_t lane_row, int64_t lane_off, uint8_t* sink,
                                                 const uint4 (&blk)[K], bool crc = false,
@@ -638,7 +638,7 @@ __device__ __forceinline__ void unit_status_pair(const DecodeParams& p, const Un
 // Unit B's loads issued one per stored block of unit A (VARIANT 7 / 8): at
 // most K + 1 loads in flight per thread instead of 2K, so a wave's stores
 // are not queued behind its own second unit's loads.
-template <int ITEM, bool SWAP, int K>
+template <int ITEM, int SWAP, int K>
 __device__ __forceinline__ void store_a_load_b(const DecodeParams& p, const Unit& UA, const RowSteps& m,
                                                uint32_t lane_row, int64_t lane_off, uint8_t* sink,
                                                const uint4 (&blk)[K], bool crc, const uint32_t* s_tab, Acc4* acc,
@@ -684,7 +684,7 @@ __device__ __forceinline__ void index_lead(const DecodeParams& p, uint32_t j, in
 // both.  (Round-1 arms 1 -- every store before the lookups -- and 2 --
 // independent chains for the two units -- measured slower and were retired
 // with the single-operator tables.)
-template <bool CRC, int ITEM, bool SWAP, int NU, int K = 8, int VARIANT = 0>
+template <bool CRC, int ITEM, int SWAP, int NU, int K = 8, int VARIANT = 0>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(NU == 1 ? 8 : 4))) void k_decode_pair(const DecodeParams p) {
     // NU == 1: the lane shift is a VALU multiply (no s_mul), so that eight
     // workgroups fit a CU's LDS
@@ -862,7 +862,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(NU == 
 // guess reloads.  (The same prologue measured slower in the CRC kernels, whose
 // 24 KiB table loads then queue behind every workgroup's data loads:
 // profiles/r03/lean/.)
-template <int ITEM, bool SWAP, int K = kDefaultBlocks>
+template <int ITEM, int SWAP, int K = kDefaultBlocks>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_decode_lead(const DecodeParams p) {
     __shared__ uint32_t s_tab[kPairTabWords];
     __shared__ uint32_t s_red[kThreads / 64];
@@ -945,7 +945,7 @@ struct RowTail {
     zhip_rowblk e[KS];
 };
 
-template <int ITEM, bool SWAP, bool CRC = false, int NQ = 4>
+template <int ITEM, int SWAP, bool CRC = false, int NQ = 4>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_decode_lead4(const DecodeParams p) {
     static_assert(NQ == 4 || NQ == 8, "four or eight chunks per workgroup");
     constexpr int KS = 16 / NQ, K0 = kDefaultBlocks - KS;  // 16 blocks per lane either way
@@ -1079,14 +1079,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 }
 
 template <int NU>
-KernelFn select_pair_nu(bool crc, int item, bool swap) {
+KernelFn select_pair_nu(bool crc, int item, int swap) {
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);
         return crc ? k_decode_pair<true, T::item, T::swap, NU> : k_decode_pair<false, T::item, T::swap, NU>;
     });
 }
 
-KernelFn select_pair_kernel(bool crc, int item, bool swap, PairForm form) {
+KernelFn select_pair_kernel(bool crc, int item, int swap, PairForm form) {
     if (form == kPairLead) {  // no data CRC, leading index-check workgroups (k_decode_lead)
         if (crc) return nullptr;
         return for_item(item, swap, [](auto t) -> KernelFn {
@@ -1124,7 +1124,7 @@ KernelFn select_pair_kernel(bool crc, int item, bool swap, PairForm form) {
 // runs the NU == 1 arm of k_decode_pair (own Horner chain, VALU lane multiply
 // by kpair11, own publication); barriers are workgroup-wide, so both halves
 // pass every one of them whatever their unit's state.
-template <bool CRC, int ITEM, bool SWAP, int K = 8>
+template <bool CRC, int ITEM, int SWAP, int K = 8>
 __global__ __launch_bounds__(2 * kThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_decode_duo(
     const DecodeParams p) {
     __shared__ uint32_t s_tab[CRC ? kPairTabWords : 1];
@@ -1366,7 +1366,7 @@ __device__ __forceinline__ void publish_lb(const DecodeParams& p, uint32_t c, ui
 // p.  k_decode_il runs it on its own grid; k_decode_il_multi runs several
 // launches' grids back to back in one (each workgroup on its launch's
 // parameters, with its index and grid size in that launch).
-template <bool CRC, int ITEM, bool SWAP, bool LEAN, bool CF, int LM, bool TUNE, int PUB, bool AFF, int PRIO, int STW>
+template <bool CRC, int ITEM, int SWAP, bool LEAN, bool CF, int LM, bool TUNE, int PUB, bool AFF, int PRIO, int STW>
 __device__ __forceinline__ void il_body(const DecodeParams& p, const uint32_t gx, const uint32_t G) {
     constexpr int K = kDefaultBlocks;
     if constexpr ((PRIO & 6) != 0) __builtin_amdgcn_s_setprio(3);
@@ -1612,7 +1612,7 @@ __device__ __forceinline__ void il_body(const DecodeParams& p, const uint32_t gx
         for (uint32_t j = g; j < p.n_idx; j += G) verify_index_pair(p, j, t, kix, s_tab, s_red[1], j == g, ipre);
 }
 
-template <bool CRC, int ITEM, bool SWAP, bool LEAN = false, bool CF = false, int LM = 0, bool TUNE = false,
+template <bool CRC, int ITEM, int SWAP, bool LEAN = false, bool CF = false, int LM = 0, bool TUNE = false,
           int PUB = 3, bool AFF = false, int PRIO = 0, int STW = 0>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(LM == 2 ? 6 : 4, LM == 2 ? 6 : 4)))
 void k_decode_il(const DecodeParams p) {
@@ -1628,7 +1628,7 @@ void k_decode_il(const DecodeParams p) {
 // launch, and no kernel boundary between them.  The launch is found with
 // scalar compares (no division); its parameter block is read through a scalar
 // base like k_decode_il's own.  Production forms only (select_il_kernel's).
-template <bool CRC, int ITEM, bool SWAP, bool AFF>
+template <bool CRC, int ITEM, int SWAP, bool AFF>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_decode_il_multi(const MultiParams m) {
     const uint32_t b = blockIdx.x;
@@ -1639,7 +1639,7 @@ void k_decode_il_multi(const MultiParams m) {
                                                                                 m.g0[i + 1] - m.g0[i]);
 }
 
-MultiFn select_il_multi_kernel(bool crc, int item, bool swap, bool aff) {  // select_il_kernel's forms
+MultiFn select_il_multi_kernel(bool crc, int item, int swap, bool aff) {  // select_il_kernel's forms
     return for_item(item, swap, [&](auto t) -> MultiFn {
         using T = decltype(t);
         if (!crc) return k_decode_il_multi<false, T::item, T::swap, false>;
@@ -1648,11 +1648,11 @@ MultiFn select_il_multi_kernel(bool crc, int item, bool swap, bool aff) {  // se
 }
 
 #if ZHIP_TUNING
-KernelFn select_il_kernel_tuned(bool crc, int item, bool swap) {  // runtime timing arms (p.tune)
+KernelFn select_il_kernel_tuned(bool crc, int item, int swap) {  // runtime timing arms (p.tune)
     return headline_item(crc, item, swap) ? k_decode_il<true, 4, false, false, false, 0, true> : nullptr;
 }
 
-KernelFn select_il_kernel_arm(bool crc, int item, bool swap, int arm) {  // ZHIP_TUNE_ARM experiments
+KernelFn select_il_kernel_arm(bool crc, int item, int swap, int arm) {  // ZHIP_TUNE_ARM experiments
     if (!headline_item(crc, item, swap)) return nullptr;
     switch (arm) {
         case kArmPub16: return k_decode_il<true, 4, false, false, false, 0, false, 0>;  // round 3: words 16 B apart
@@ -1700,22 +1700,22 @@ int launch_dv_check(const zhip_dv_ref* d_refs, uint32_t n_refs, hipStream_t stre
 }
 
 #if ZHIP_TUNING
-KernelFn select_il_kernel_lean(bool crc, int item, bool swap) {  // kTuneIlLean (4-byte LE CRC item type only)
+KernelFn select_il_kernel_lean(bool crc, int item, int swap) {  // kTuneIlLean (4-byte LE CRC item type only)
     return headline_item(crc, item, swap) ? k_decode_il<true, 4, false, true> : nullptr;
 }
 
-KernelFn select_il_kernel_cf(bool crc, int item, bool swap) {  // kTuneCfLookup timing arm (results invalid)
+KernelFn select_il_kernel_cf(bool crc, int item, int swap) {  // kTuneCfLookup timing arm (results invalid)
     return headline_item(crc, item, swap) ? k_decode_il<true, 4, false, false, true> : nullptr;
 }
 
-KernelFn select_il_kernel_regmul(bool crc, int item, bool swap, bool occ6) {  // kTuneIlRegMul / kTuneIlOcc6 arms
+KernelFn select_il_kernel_regmul(bool crc, int item, int swap, bool occ6) {  // kTuneIlRegMul / kTuneIlOcc6 arms
     if (!headline_item(crc, item, swap)) return nullptr;
     return occ6 ? k_decode_il<true, 4, false, false, false, 2> : k_decode_il<true, 4, false, false, false, 1>;
 }
 
 #endif
 
-KernelFn select_il_kernel(bool crc, int item, bool swap, bool aff) {  // aff: ZHIP_DF_WHOLE (CRC chains)
+KernelFn select_il_kernel(bool crc, int item, int swap, bool aff) {  // aff: ZHIP_DF_WHOLE (CRC chains)
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);
         if (!crc) return k_decode_il<false, T::item, T::swap>;
@@ -1786,7 +1786,7 @@ __device__ __forceinline__ void publish_ilq(const DecodeParams& p, uint32_t c, u
     }
 }
 
-template <int ITEM, bool SWAP, int NQ, bool GLDS>
+template <int ITEM, int SWAP, int NQ, bool GLDS>
 __global__ __launch_bounds__(NQ * kThreads) __attribute__((amdgpu_waves_per_eu(NQ == 4 ? 8 : NQ == 2 ? 6 : 4)))
 void k_decode_ilq(const DecodeParams p) {
     constexpr int K = kDefaultBlocks;
@@ -1963,7 +1963,7 @@ __device__ __forceinline__ void build_il_tables_lds(uint32_t* s, int t, const ui
     for (int j = 0; j < 4; ++j) s[kPairA4 + 256 * j + t] = lane_part(32 + 8 * j);  // A4 byte tables
 }
 
-template <int ITEM, bool SWAP>
+template <int ITEM, int SWAP>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_decode_ilc(
     const DecodeParams p) {
     constexpr int K = kDefaultBlocks;
@@ -2087,7 +2087,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
 // an index-missing or failing inner chunk redoes the unit on a slow path
 // (drain, reload or fill, restore, re-hash).  launch_decode admits it only
 // with a prediction (zhip_predict).
-template <int ITEM, bool SWAP>
+template <int ITEM, int SWAP>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_decode_ilp(
     const DecodeParams p) {
     constexpr int K = kDefaultBlocks;
@@ -2243,7 +2243,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
 // of its segment's half h at 16 t: one chain through the pair kernel's
 // A_4096 tables, lane constants per (half unit, lane) from capi.cpp; up to
 // 64 workgroups per chunk publish per 32-workgroup word with a second level.
-template <int ITEM, bool SWAP, bool LB = false, bool AFF = false>
+template <int ITEM, int SWAP, bool LB = false, bool AFF = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_decode_ilh(
     const DecodeParams p) {
     constexpr int KW = 4;
@@ -2369,7 +2369,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
 // fewer chunks than CUs are in flight: LB (the look-back finalizer) with the
 // AFF form for ZHIP_DF_WHOLE launches; the tuning build adds the returning
 // publication (arm 41) and LB without AFF (arm 59)
-KernelFn select_ilh_kernel(int item, bool swap, bool lb, bool aff) {  // CRC chains only
+KernelFn select_ilh_kernel(int item, int swap, bool lb, bool aff) {  // CRC chains only
     if (!ZHIP_TUNING && !lb) return nullptr;
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);
@@ -2417,7 +2417,7 @@ __device__ __forceinline__ uint32_t lanemul3_w(const uint32_t* s_mul, int t, uin
 // column: the run end's LDS reads halve.  MIX (tuning arm 42): the waves of
 // the second 256 lanes multiply in registers, the first through the LDS
 // column, so the run end's lookups and VALU work overlap.
-template <int ITEM, bool SWAP, int NT, bool LMR = false, bool MIX = false, bool AFF = false, bool SPL = false,
+template <int ITEM, int SWAP, int NT, bool LMR = false, bool MIX = false, bool AFF = false, bool SPL = false,
           bool LB = false>
 __global__ __launch_bounds__(NT) void k_decode_ilw(const DecodeParams p) {
     constexpr int KW = 2048 / NT;  // blocks per lane
@@ -2547,7 +2547,7 @@ __global__ __launch_bounds__(NT) void k_decode_ilw(const DecodeParams p) {
 // production: 512 lanes, the LDS lane multiply (small grids, launch_decode),
 // the AFF form for ZHIP_DF_WHOLE launches; the tuning build adds 1024 lanes
 // and the register multiply (kIlw512Half: half the waves, arm 42)
-KernelFn select_ilw_kernel(int item, bool swap, IlwForm form, bool lmr, bool aff) {  // CRC chains only
+KernelFn select_ilw_kernel(int item, int swap, IlwForm form, bool lmr, bool aff) {  // CRC chains only
     if (!ZHIP_TUNING && (form != kIlw512 || lmr)) return nullptr;
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);
@@ -2564,17 +2564,17 @@ KernelFn select_ilw_kernel(int item, bool swap, IlwForm form, bool lmr, bool aff
 }
 
 #if ZHIP_TUNING
-KernelFn select_ilp_kernel(int item, bool swap) {  // CRC chains only
+KernelFn select_ilp_kernel(int item, int swap) {  // CRC chains only
     return for_item(item, swap, [](auto t) -> KernelFn { return k_decode_ilp<decltype(t)::item, decltype(t)::swap>; });
 }
 
-KernelFn select_ilc_kernel(int item, bool swap) {  // CRC chains only
+KernelFn select_ilc_kernel(int item, int swap) {  // CRC chains only
     return for_item(item, swap, [](auto t) -> KernelFn { return k_decode_ilc<decltype(t)::item, decltype(t)::swap>; });
 }
 #endif
 
 #if ZHIP_TUNING
-KernelFn select_ilq_kernel(int item, bool swap, int nq, bool glds) {  // CRC chains only
+KernelFn select_ilq_kernel(int item, int swap, int nq, bool glds) {  // CRC chains only
     if (item != 4) return nullptr;  // 4-byte items only
     auto pick = [&](auto t) -> KernelFn {
         using T = decltype(t);
@@ -2621,7 +2621,7 @@ __device__ __forceinline__ void publish_xw(const DecodeParams& p, uint32_t c, ui
     publish_il(p, c, sg, ns, V ^ lo, stored, (int)l);
 }
 
-template <bool CRC, int ITEM, bool SWAP>
+template <bool CRC, int ITEM, int SWAP>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_decode_xw(const DecodeParams p) {
     constexpr int K = kDefaultBlocks;
     __shared__ uint32_t s_tab[CRC ? kPairTabWords : 1];
@@ -2730,7 +2730,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
 }
 
 #if ZHIP_TUNING
-KernelFn select_xw_kernel(bool crc, int item, bool swap) {
+KernelFn select_xw_kernel(bool crc, int item, int swap) {
     if (!crc) return nullptr;
     return for_item(item, swap, [](auto t) -> KernelFn {
         return k_decode_xw<true, decltype(t)::item, decltype(t)::swap>;
@@ -2738,14 +2738,14 @@ KernelFn select_xw_kernel(bool crc, int item, bool swap) {
 }
 #endif
 
-KernelFn select_duo_kernel(bool crc, int item, bool swap) {
+KernelFn select_duo_kernel(bool crc, int item, int swap) {
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);
         return crc ? k_decode_duo<true, T::item, T::swap> : k_decode_duo<false, T::item, T::swap>;
     });
 }
 
-KernelFn select_rows_kernel(bool crc, int item, bool swap, int k) {
+KernelFn select_rows_kernel(bool crc, int item, int swap, int k) {
 #if ZHIP_TUNING
     if (k == 4) {  // 16 KiB units (tuning arm)
         return headline_item(crc, item, swap) ? k_decode_rows<true, 4, false, 4> : nullptr;

@@ -23,6 +23,7 @@
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
 #include "zhip_dispatch.h"
+#include "zhip_fill_eq.h"
 #include "zhip_device.h"
 #include "zhip_decode_common.h"
 
@@ -52,28 +53,11 @@ __device__ __forceinline__ void store_nt16_a1(uint8_t* a, uint4 v) {  // any ali
     __builtin_nontemporal_store(w, (zhip_gv4u_a1tw*)(reinterpret_cast<uintptr_t>(a)));
 }
 
-// NDBuffer.all_equal against the fill (buffer/core.py:534-558): bitwise, except
-// that any NaN equals a NaN fill; 16 native-order bytes.
-template <int ITEM>
+// chunk_is_empty over 16 native-order bytes: the rule of zhip_fill_eq.h (SWAP:
+// the item mode, whose complex bit selects the complex64 comparison).
+template <int ITEM, int SWAP = 0>
 __device__ __forceinline__ bool block_eq_fill_e(uint4 v, const EncodeParams& p) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    bool all = true;
-#pragma unroll
-    for (int j = 0; j < 16 / ITEM; ++j) {
-        if constexpr (ITEM == 8) {
-            const uint64_t x = ((uint64_t)w[2 * j + 1] << 32) | w[2 * j];
-            const bool e = w[2 * j] == p.fill[0] && w[2 * j + 1] == p.fill[1];
-            all = all && (e || (p.fill_nan && (x & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull));
-        } else {
-            constexpr uint32_t m = ITEM == 4 ? 0xFFFFFFFFu : ((1u << (8 * ITEM)) - 1u);
-            const uint32_t x = (w[(j * ITEM) / 4] >> (8 * ((j * ITEM) % 4))) & m;
-            bool e = x == (p.fill[0] & m);
-            if constexpr (ITEM == 4) e = e || (p.fill_nan && (x & 0x7FFFFFFFu) > 0x7F800000u);
-            if constexpr (ITEM == 2) e = e || (p.fill_nan && (x & 0x7FFFu) > 0x7C00u);
-            all = all && e;
-        }
-    }
-    return all;
+    return block_eq_fill_bits<ITEM, ITEM == 8 && (SWAP & kModeCplx) != 0>(v.x, v.y, v.z, v.w, 16u, p.fill, p.fill_nan);
 }
 
 struct TileMap4 {
@@ -120,7 +104,7 @@ __device__ __forceinline__ uint4 tile_get16(const uint8_t* s, uint32_t r, uint32
 // CRC verdicts (zarrhip.h: a non-returning xor per workgroup, the first
 // workgroup of a chunk checks the previous launch's verdict).  Graph-timed on
 // C3 (profiles/r04/b/arms_c3.jsonl): returning 29.30 us, deferred 29.85.
-template <bool CRC, int ITEM, bool SWAP, int PUB = 3>
+template <bool CRC, int ITEM, int SWAP, int PUB = 3>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_decode_tile4(
     const DecodeParams p) {
     constexpr int kPer = 16 / ITEM;                // rows per 16-byte out piece
@@ -307,7 +291,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 // k_decode_tile4 on C3 (31.5-32.0 vs 31.2-31.6 us graph-timed,
 // profiles/r03/tile4f/) -- its loads are 64-byte pieces of 16 rows per wave
 // instruction instead of 256-byte rows, two requests per 128-byte line.
-template <int ITEM, bool SWAP>
+template <int ITEM, int SWAP>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_decode_tile4f(
     const DecodeParams p) {
     constexpr int kPer = 16 / ITEM;
@@ -478,7 +462,7 @@ struct TileMapN {
 // instead of 32 arrivals on the chunk's one word.
 // BT (tuning arm 67): the chain through byte tables (crc_block4_t): 24 KiB of
 // LDS per workgroup instead of 40, six resident per CU instead of four
-template <int ITEM, bool SWAP, int NT = kTiles, bool SPL = false, bool BT = false>
+template <int ITEM, int SWAP, int NT = kTiles, bool SPL = false, bool BT = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_decode_tile4w(
     const DecodeParams p) {
     constexpr int kPer = 16 / ITEM;
@@ -657,7 +641,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 // lane multiply, one reduction and one XOR + arrival pair per workgroup (any
 // number of groups per chunk).  PUB as in k_decode_tile4 (2: deferred CRC
 // verdicts, production; 0: the returning two-level arrival, arm 2).
-template <bool CRC, int ITEM, bool SWAP, int PUB = 2>
+template <bool CRC, int ITEM, int SWAP, int PUB = 2>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_decode_tileg(
     const DecodeParams p) {
     constexpr int kPer = 16 / ITEM;
@@ -843,7 +827,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 //   chunk's last workgroup polls, the others retire after a non-returning xor)
 // BT (tuning arm 66): the chain through byte tables (crc_block4_t), 24 KiB of
 //   LDS instead of 40
-template <int ITEM, bool SWAP, int PUB = 2, int NT = kTiles, bool LT = false, bool SPR = false, bool LB = false,
+template <int ITEM, int SWAP, int PUB = 2, int NT = kTiles, bool LT = false, bool SPR = false, bool LB = false,
           bool BT = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_decode_tilegw(
     const DecodeParams p) {
@@ -1031,7 +1015,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 // NT: tiles per workgroup -- 4, or 2 (twice the workgroups: two residency
 // rounds, as k_decode_tile4w's two-tile form; up to 32 workgroups per chunk
 // publish per half-chunk word with a second level, as k_encode_il)
-template <bool CRC, int ITEM, bool SWAP, int NT = kTiles>
+template <bool CRC, int ITEM, int SWAP, int NT = kTiles>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_tile4(
     const EncodeParams p) {
     constexpr int kPer = 16 / ITEM;
@@ -1117,7 +1101,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 #pragma unroll
         for (int k = 0; k < kPasses; ++k) {
             const uint4 v = tile_get16<ITEM>(s_tile, 16 * k + row0, col);
-            eq = eq && block_eq_fill_e<ITEM>(v, p);
+            eq = eq && block_eq_fill_e<ITEM, SWAP>(v, p);
             const uint4 e = swap_block<ITEM, SWAP>(v);
             store_nt16_a1(cp + tm.e[j].tbase + (row0 + 16u * k) * sq + col, e);
             if constexpr (CRC)
@@ -1227,7 +1211,7 @@ __device__ __forceinline__ TileGeo encode_tile_geo(const EncodeParams& p, uint32
     return g;
 }
 
-template <bool CRC, int ITEM, bool SWAP>
+template <bool CRC, int ITEM, int SWAP>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_tile(
     const EncodeParams p) {
     constexpr int kPer = 16 / ITEM;
@@ -1362,7 +1346,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             uint4 e = make_uint4(0, 0, 0, 0);
             if ((int32_t)row < geo[j].rows_here && (int32_t)col < geo[j].cols_here) {
                 const uint4 v = tile_get16<ITEM>(s_tile, row, col);
-                eq = eq && block_eq_fill_e<ITEM>(v, p);
+                eq = eq && block_eq_fill_e<ITEM, SWAP>(v, p);
                 e = swap_block<ITEM, SWAP>(v);
                 store_nt16_a1(cp + geo[j].tbase + row * sq + col, e);
             }
@@ -1433,7 +1417,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 //   (fold4_t: the state x^96 times the single accumulator's, undone by g_c96
 //   in the lane multiply): 16 + 4 lookups per tile more, 8 KiB of tables
 //   instead of 16 -- 28 KiB of LDS, five workgroups per CU instead of four
-template <bool CRC, int ITEM, bool SWAP, int NT = kTiles, bool SPR = false, bool LB = false, bool A4C = false>
+template <bool CRC, int ITEM, int SWAP, int NT = kTiles, bool SPR = false, bool LB = false, bool A4C = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_tileg(
     const EncodeParams p) {
     constexpr int kPer = 16 / ITEM;
@@ -1536,7 +1520,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             uint4 e = make_uint4(0, 0, 0, 0);
             if ((int32_t)row < rows && (int32_t)col < cols) {
                 const uint4 v = tile_get16<ITEM>(s_tile, row, col);
-                eq = eq && block_eq_fill_e<ITEM>(v, p);
+                eq = eq && block_eq_fill_e<ITEM, SWAP>(v, p);
                 e = swap_block<ITEM, SWAP>(v);
                 store_nt16_a1(cp + (size_t)(t0 + j) * p.g_step_t + row * sq + col, e);
             }
@@ -1606,13 +1590,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     }
 }
 
-EncodeFn select_encode_tileg_kernel(bool crc, int item, bool swap, EncTilegForm form) {
+EncodeFn select_encode_tileg_kernel(bool crc, int item, int swap, EncTilegForm form) {
 #if ZHIP_TUNING
     if (form == kEtgFourSpread || form == kEtgTwoSpread || form == kEtgLookBack || form == kEtgA4) {
         // arms 47 / 50: four / two tiles, arrival words on lines of their own; arm 63: four tiles,
         // the look-back finalizer; arm 68: four accumulators through one byte-table operator
         if (!crc) return nullptr;
-        return for_item(item, swap, [&](auto t) -> EncodeFn {
+        return for_item_enc(item, swap, [&](auto t) -> EncodeFn {
             using T = decltype(t);
             return form == kEtgFourSpread ? k_encode_tileg<true, T::item, T::swap, 4, true>
                    : form == kEtgLookBack ? k_encode_tileg<true, T::item, T::swap, 4, true, true>
@@ -1623,32 +1607,32 @@ EncodeFn select_encode_tileg_kernel(bool crc, int item, bool swap, EncTilegForm 
 #endif
     if (form == kEtgTwo) {  // CRC layouts only
         if (!crc) return nullptr;
-        return for_item(item, swap, [](auto t) -> EncodeFn {
+        return for_item_enc(item, swap, [](auto t) -> EncodeFn {
             return k_encode_tileg<true, decltype(t)::item, decltype(t)::swap, 2>;
         });
     }
-    return for_item(item, swap, [&](auto t) -> EncodeFn {
+    return for_item_enc(item, swap, [&](auto t) -> EncodeFn {
         using T = decltype(t);
         return crc ? k_encode_tileg<true, T::item, T::swap> : k_encode_tileg<false, T::item, T::swap>;
     });
 }
 
-EncodeFn select_encode_tile_kernel(bool crc, int item, bool swap) {
-    return for_item(item, swap, [&](auto t) -> EncodeFn {
+EncodeFn select_encode_tile_kernel(bool crc, int item, int swap) {
+    return for_item_enc(item, swap, [&](auto t) -> EncodeFn {
         using T = decltype(t);
         return crc ? k_encode_tile<true, T::item, T::swap> : k_encode_tile<false, T::item, T::swap>;
     });
 }
 
 // two: the two-tile form (CRC layouts whose plan built its constants)
-EncodeFn select_encode_tile4_kernel(bool crc, int item, bool swap, bool two) {
+EncodeFn select_encode_tile4_kernel(bool crc, int item, int swap, bool two) {
     if (two) {
         if (!crc) return nullptr;
-        return for_item(item, swap, [](auto t) -> EncodeFn {
+        return for_item_enc(item, swap, [](auto t) -> EncodeFn {
             return k_encode_tile4<true, decltype(t)::item, decltype(t)::swap, 2>;
         });
     }
-    return for_item(item, swap, [&](auto t) -> EncodeFn {
+    return for_item_enc(item, swap, [&](auto t) -> EncodeFn {
         using T = decltype(t);
         return crc ? k_encode_tile4<true, T::item, T::swap> : k_encode_tile4<false, T::item, T::swap>;
     });
@@ -1656,7 +1640,7 @@ EncodeFn select_encode_tile4_kernel(bool crc, int item, bool swap, bool two) {
 
 // defer: ZHIP_DF_DEFER (deferred CRC verdicts, PUB 2); otherwise the returning
 // publication (PUB 0), whose launch reports a mismatch itself
-KernelFn select_tileg_kernel(bool crc, int item, bool swap, bool defer) {
+KernelFn select_tileg_kernel(bool crc, int item, int swap, bool defer) {
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);
         if (!crc) return k_decode_tileg<false, T::item, T::swap>;
@@ -1666,7 +1650,7 @@ KernelFn select_tileg_kernel(bool crc, int item, bool swap, bool defer) {
 
 // (kTgwTwo: always the returning publication on spread lines; the forms past
 // kTgwFour exist in the tuning build only and select as kTgwFour elsewhere)
-KernelFn select_tilegw_kernel(int item, bool swap, bool defer, TilegwForm form) {  // CRC chains only
+KernelFn select_tilegw_kernel(int item, int swap, bool defer, TilegwForm form) {  // CRC chains only
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);
         if (form == kTgwTwo) return k_decode_tilegw<T::item, T::swap, 0, 2, false, true>;
@@ -1681,14 +1665,14 @@ KernelFn select_tilegw_kernel(int item, bool swap, bool defer, TilegwForm form) 
     });
 }
 
-KernelFn select_tile4w_kernel(int item, bool swap) {  // CRC chains only
+KernelFn select_tile4w_kernel(int item, int swap) {  // CRC chains only
     return for_item(item, swap, [](auto t) -> KernelFn { return k_decode_tile4w<decltype(t)::item, decltype(t)::swap>; });
 }
 
 // two tiles per workgroup (production where the plan built its constants);
 // the tuning build adds one tile per workgroup (arm 37), the split
 // publication (arm 49) and the byte-table chains (arm 67)
-KernelFn select_tile2w_kernel(int item, bool swap, Tile2wForm form) {  // CRC chains only
+KernelFn select_tile2w_kernel(int item, int swap, Tile2wForm form) {  // CRC chains only
     if (!ZHIP_TUNING && form != kT2wTwo) return nullptr;
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);
@@ -1702,12 +1686,12 @@ KernelFn select_tile2w_kernel(int item, bool swap, Tile2wForm form) {  // CRC ch
 }
 
 #if ZHIP_TUNING
-KernelFn select_tile4f_kernel(int item, bool swap) {  // CRC chains only
+KernelFn select_tile4f_kernel(int item, int swap) {  // CRC chains only
     return for_item(item, swap, [](auto t) -> KernelFn { return k_decode_tile4f<decltype(t)::item, decltype(t)::swap>; });
 }
 #endif
 
-KernelFn select_tile4_kernel(bool crc, int item, bool swap) {
+KernelFn select_tile4_kernel(bool crc, int item, int swap) {
 #if ZHIP_TUNING
     if (headline_item(crc, item, swap)) {
         if (g_tune_arm == kArmPub16) return k_decode_tile4<true, 4, false, 0>;  // words 16 B apart

@@ -27,48 +27,17 @@
 #include "zhip_gf2.h"
 #include "zhip_internal.h"
 #include "zhip_dispatch.h"
+#include "zhip_fill_eq.h"
 #include "zhip_decode_common.h"
 
 namespace zhip {
 
-// Element equality with the fill value as NDBuffer.all_equal defines it:
-// bitwise, except that any NaN equals a NaN fill (equal_nan=True); a 0.0 fill
-// compares bit patterns (so -0.0 != 0.0), which bitwise equality gives.
-template <int ITEM>
-__device__ __forceinline__ bool item_eq_fill(uint32_t lo, uint32_t hi, const EncodeParams& p) {
-    if constexpr (ITEM == 8) {
-        const bool eq = lo == p.fill[0] && hi == p.fill[1];
-        if (!p.fill_nan) return eq;
-        const uint64_t v = ((uint64_t)hi << 32) | lo;
-        return eq || (v & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull;
-    } else {
-        constexpr uint32_t mask = ITEM == 4 ? 0xFFFFFFFFu : ((1u << (8 * ITEM)) - 1u);
-        const bool eq = (lo & mask) == (p.fill[0] & mask);
-        if (!p.fill_nan) return eq;
-        if constexpr (ITEM == 4) return eq || (lo & 0x7FFFFFFFu) > 0x7F800000u;
-        if constexpr (ITEM == 2) return eq || (lo & 0x7FFFu) > 0x7C00u;
-        return eq;
-    }
-}
-
-template <int ITEM>
+// chunk_is_empty over one 16-byte block (native order, items whose first
+// byte lies below `valid`): the rule of zhip_fill_eq.h; SWAP is the item mode,
+// whose complex bit selects the complex64 comparison.
+template <int ITEM, int SWAP = 0>
 __device__ __forceinline__ bool block_eq_fill(uint4 v, uint32_t valid, const EncodeParams& p) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    bool all = true;
-    constexpr int kItems = 16 / ITEM;
-#pragma unroll
-    for (int j = 0; j < kItems; ++j) {
-        if ((uint32_t)(j * ITEM) >= valid) break;
-        uint32_t lo, hi = 0;
-        if constexpr (ITEM == 8) {
-            lo = w[2 * j];
-            hi = w[2 * j + 1];
-        } else {
-            lo = w[(j * ITEM) / 4] >> (8 * ((j * ITEM) % 4));
-        }
-        all = all && item_eq_fill<ITEM>(lo, hi, p);
-    }
-    return all;
+    return block_eq_fill_bits<ITEM, ITEM == 8 && (SWAP & kModeCplx) != 0>(v.x, v.y, v.z, v.w, valid, p.fill, p.fill_nan);
 }
 
 template <int ITEM>
@@ -138,7 +107,7 @@ __device__ __forceinline__ void put_le_u32(uint8_t* d, uint32_t v) {  // any ali
     d[3] = (uint8_t)(v >> 24);
 }
 
-template <bool CRC, bool FAST, int ITEM, bool SWAP>
+template <bool CRC, bool FAST, int ITEM, int SWAP>
 __global__ __launch_bounds__(kThreads) void k_encode(const EncodeParams p) {
     constexpr int K = kDefaultBlocks;
     __shared__ uint32_t s_tab[CRC ? 16 * 256 : 1];
@@ -178,7 +147,7 @@ __global__ __launch_bounds__(kThreads) void k_encode(const EncodeParams p) {
             const int32_t o = seg_lo + kWgStride * k + 16 * t;
             if (o < 0 || (uint32_t)o >= p.g.nbytes) continue;
             const uint32_t valid = p.g.nbytes - (uint32_t)o;
-            alleq = alleq && block_eq_fill<ITEM>(blk[k], valid, p);
+            alleq = alleq && block_eq_fill<ITEM, SWAP>(blk[k], valid, p);
             blk[k] = mask_tail(swap_block<ITEM, SWAP>(blk[k]), o, p.g.nbytes);
             store_block(cp, o, blk[k], valid, al4);
         }
@@ -267,7 +236,7 @@ struct EncRowSteps {
 // (one accumulator per word through A4096, the 11/11/10 pair tables: 12
 // lookups per block instead of 16, folded at the run end -- k_decode_pair's
 // CRC, zhip_decode_common.h)
-template <bool CRC, int ITEM, bool SWAP, typename ACC>
+template <bool CRC, int ITEM, int SWAP, typename ACC>
 __device__ __forceinline__ void enc_unit(const EncodeParams& p, const zhip_chunk& ch, uint32_t sidx, bool live,
                                         const EncRowSteps& m, uint32_t lane_row, const uint4 (&blk)[kDefaultBlocks],
                                         const uint32_t* s_tab, ACC& acc, bool& alleq, int t) {
@@ -280,7 +249,7 @@ __device__ __forceinline__ void enc_unit(const EncodeParams& p, const zhip_chunk
         const int32_t o = seg_lo + kWgStride * k;
         const bool in_sel = lane_row - m.e[k].lo < (uint32_t)(m.e[k].hi - m.e[k].lo);
         const uint4 v = in_sel ? blk[k] : f;  // _merge_chunk_array: outside the selection = fill
-        alleq = alleq && block_eq_fill<ITEM>(v, 16u, p);
+        alleq = alleq && block_eq_fill<ITEM, SWAP>(v, 16u, p);
         const uint4 e = swap_block<ITEM, SWAP>(v);
         enc_store16(live && o >= 0 ? cp + o + 16 * t : sink, e);  // every path stores: static count
         if constexpr (CRC) {
@@ -384,7 +353,7 @@ __device__ __forceinline__ void enc_run_end_pair(const EncodeParams& p, const zh
 // instead of the byte-position tables: 12 lookups per block instead of 16,
 // graph-timed on C2 30.7-30.9 vs 30.5-30.6 us (profiles/r04/g/enc_arms.jsonl):
 // the encode is not bound by its lookups
-template <bool CRC, int ITEM, bool SWAP, bool T11 = false>
+template <bool CRC, int ITEM, int SWAP, bool T11 = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_pair(const EncodeParams p) {
     constexpr int K = kDefaultBlocks;
     using ACC = typename std::conditional<T11, Acc4, uint32_t>::type;
@@ -501,7 +470,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 // AFF (tuning arm 46): ZHIP_DF_WHOLE launches of plans with aff_ok take the
 // destinations from aff_rowblk instead of the row map (k_decode_il's AFF);
 // graph-timed 0.5 us slower on the C2 encode, not adopted.
-template <int ITEM, bool SWAP, bool AFF = false>
+template <int ITEM, int SWAP, bool AFF = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_encode_il(const EncodeParams p) {
     constexpr int K = kDefaultBlocks;
     __shared__ uint32_t s_tab[kPairTabWords];
@@ -567,7 +536,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         const int32_t o = lo_frame + kWgStride * (int32_t)(st0 + S * (uint32_t)k);
         const bool in = lane_row - m[k].lo < (uint32_t)(m[k].hi - m[k].lo);
         const uint4 v = in ? A[k] : f;
-        eq = eq && block_eq_fill<ITEM>(v, 16u, p);
+        eq = eq && block_eq_fill<ITEM, SWAP>(v, 16u, p);
         const uint4 e = swap_block<ITEM, SWAP>(v);
         enc_store16(o >= 0 ? cp + o + 16 * t : sink, e);
         if (o >= 0) crc_block4(s_tab, acc, e);
@@ -608,8 +577,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     p.status[c] = st;
 }
 
-static EncodeFn pick_encode_il(int item, bool swap, bool aff) {
-    return for_item(item, swap, [&](auto t) -> EncodeFn {
+static EncodeFn pick_encode_il(int item, int swap, bool aff) {
+    return for_item_enc(item, swap, [&](auto t) -> EncodeFn {
         using T = decltype(t);
 #if ZHIP_TUNING
         if (aff) return k_encode_il<T::item, T::swap, true>;  // (arm 46)
@@ -625,7 +594,7 @@ static EncodeFn pick_encode_il(int item, bool swap, bool aff) {
 // only the last four steps of each.  The workgroup owns its chunks whole: CRC
 // and non-empty bit reduce in LDS and lanes 0..3 write trailer, status and flag
 // of one chunk each (no publication word, no zeroed flags).
-template <bool CRC, int ITEM, bool SWAP>
+template <bool CRC, int ITEM, int SWAP>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_quad(const EncodeParams p) {
     constexpr int NQ = 4, KS = kDefaultBlocks / 2, K0 = kDefaultBlocks - KS;
     __shared__ uint32_t s_tab[CRC ? 16 * 256 : 1];
@@ -688,7 +657,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             const int32_t o = seg_lo + kWgStride * (K0 + k);
             const bool in_sel = lane_row - e.lo < (uint32_t)(e.hi - e.lo);
             const uint4 v = in_sel ? blk[i][k] : f;  // _merge_chunk_array: outside the selection = fill
-            eq = eq && block_eq_fill<ITEM>(v, 16u, p);
+            eq = eq && block_eq_fill<ITEM, SWAP>(v, 16u, p);
             const uint4 w = swap_block<ITEM, SWAP>(v);
             enc_store16(live[i] && o >= 0 ? cp + o + 16 * t : sink, w);
             if constexpr (CRC)
@@ -721,26 +690,26 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 }
 
 
-static EncodeFn pick_encode_quad(bool crc, int item, bool swap) {
-    return for_item(item, swap, [&](auto t) -> EncodeFn {
+static EncodeFn pick_encode_quad(bool crc, int item, int swap) {
+    return for_item_enc(item, swap, [&](auto t) -> EncodeFn {
         using T = decltype(t);
         return crc ? k_encode_quad<true, T::item, T::swap> : k_encode_quad<false, T::item, T::swap>;
     });
 }
 
 template <bool CRC, bool FAST>
-static EncodeFn pick_encode(int item, bool swap) {
-    return for_item(item, swap, [](auto t) -> EncodeFn {
+static EncodeFn pick_encode(int item, int swap) {
+    return for_item_enc(item, swap, [](auto t) -> EncodeFn {
         return k_encode<CRC, FAST, decltype(t)::item, decltype(t)::swap>;
     });
 }
 
-static EncodeFn pick_encode_pair(bool crc, int item, bool swap) {
+static EncodeFn pick_encode_pair(bool crc, int item, int swap) {
 #if ZHIP_TUNING
     // (11/11/10 tables)
     if (g_tune_arm == kArmPub16 && headline_item(crc, item, swap)) return k_encode_pair<true, 4, false, true>;
 #endif
-    return for_item(item, swap, [&](auto t) -> EncodeFn {
+    return for_item_enc(item, swap, [&](auto t) -> EncodeFn {
         using T = decltype(t);
         return crc ? k_encode_pair<true, T::item, T::swap> : k_encode_pair<false, T::item, T::swap>;
     });
@@ -752,7 +721,8 @@ struct EncLaunch {
     const EncodeParams& p;
     hipStream_t stream;
     int max_grid;  // CUs * 8
-    bool crc, swap;
+    bool crc;
+    int swap;  // item_mode(): ZHIP_LF_SWAP | 2 * ZHIP_LF_COMPLEX
     int item;
 };
 
@@ -850,7 +820,8 @@ static int launch_encode_persistent(const EncLaunch& L) {
 // (tile4, grouped tiles, tile), the row-mapped kernels, else the generic
 // persistent k_encode.
 int launch_encode(const EncodeParams& p, hipStream_t stream, int max_grid) {
-    const EncLaunch L = {p, stream, max_grid, (p.lflags & ZHIP_LF_CRC) != 0, (p.lflags & ZHIP_LF_SWAP) != 0, p.g.itemsize};
+    const EncLaunch L = {p, stream, max_grid, (p.lflags & ZHIP_LF_CRC) != 0,
+                         item_mode(p.lflags, (int)p.g.itemsize), p.g.itemsize};
     if (p.tile4) return launch_encode_tile4(L);
     if (p.tile == 2) return launch_encode_tileg(L);
     if (p.tile) return launch_encode_tile(L);

@@ -15,10 +15,16 @@ __device__ __forceinline__ uint32_t bswap_item(uint32_t x, int item) {
     return x;
 }
 
-template <int ITEM, bool SWAP>
+// SWAP is the item mode of zhip_dispatch.h: bit 0 swaps, bit 1 on an 8-byte
+// item is complex64, whose swap reverses each 4-byte half in place
+// (BytesCodec on a '>c8' array; numpy byteswaps the components).
+template <int ITEM, int SWAP>
 __device__ __forceinline__ uint4 swap_block(uint4 v) {
-    if constexpr (!SWAP || ITEM == 1) {
+    if constexpr (!(SWAP & 1) || ITEM == 1) {
         return v;
+    } else if constexpr (ITEM == 8 && (SWAP & 2)) {
+        return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z),
+                          __builtin_bswap32(v.w));
     } else if constexpr (ITEM == 8) {
         return make_uint4(__builtin_bswap32(v.y), __builtin_bswap32(v.x), __builtin_bswap32(v.w),
                           __builtin_bswap32(v.z));
@@ -150,24 +156,26 @@ __device__ __forceinline__ bool sel_offset(const Geom& g, const zhip_sel& s, uin
     return ok;
 }
 
-template <int ITEM, bool SWAP>
+template <int ITEM, int SWAP>
 __device__ __forceinline__ void store_item(uint8_t* dst, uint32_t lo, uint32_t hi) {
     if constexpr (ITEM == 1) {
         *dst = (uint8_t)lo;
     } else if constexpr (ITEM == 2) {
         uint16_t v = (uint16_t)lo;
-        if constexpr (SWAP) v = (uint16_t)((v >> 8) | (v << 8));
+        if constexpr ((SWAP & 1) != 0) v = (uint16_t)((v >> 8) | (v << 8));
         *reinterpret_cast<uint16_t*>(dst) = v;
     } else if constexpr (ITEM == 4) {
-        *reinterpret_cast<uint32_t*>(dst) = SWAP ? __builtin_bswap32(lo) : lo;
+        *reinterpret_cast<uint32_t*>(dst) = (SWAP & 1) ? __builtin_bswap32(lo) : lo;
     } else {
-        uint2 v = SWAP ? make_uint2(__builtin_bswap32(hi), __builtin_bswap32(lo)) : make_uint2(lo, hi);
+        uint2 v = !(SWAP & 1)  ? make_uint2(lo, hi)
+                  : (SWAP & 2) ? make_uint2(__builtin_bswap32(lo), __builtin_bswap32(hi))
+                               : make_uint2(__builtin_bswap32(hi), __builtin_bswap32(lo));
         *reinterpret_cast<uint2*>(dst) = v;
     }
 }
 
 // Scatter one 16-byte block (chunk bytes [o, o+16), whole items) element by element.
-template <int ITEM, bool SWAP>
+template <int ITEM, int SWAP>
 __device__ __forceinline__ void scatter_block_generic(const Geom& g, uint8_t* out, const zhip_sel& s,
                                                       int64_t out_off, int32_t o, uint4 v) {
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -191,7 +199,7 @@ __device__ __forceinline__ void scatter_block_generic(const Geom& g, uint8_t* ou
 
 // Whole-row fast path: rows of the innermost stored dim are fully selected,
 // contiguous in out and a multiple of 16 bytes, out rows 16-byte aligned.
-template <int ITEM, bool SWAP, bool NT = false>
+template <int ITEM, int SWAP, bool NT = false>
 __device__ __forceinline__ void scatter_block_rows(const Geom& g, uint8_t* out, const zhip_sel& s,
                                                    int64_t out_off, int32_t o, uint4 v) {
     const uint32_t r = fdiv_apply((uint32_t)o, g.drow.m, g.drow.s);

@@ -516,36 +516,36 @@ enum EncTilegForm {
 };
 
 // decode_rows.hip
-KernelFn select_rows_kernel(bool crc, int item, bool swap, int k);
-KernelFn select_pair_kernel(bool crc, int item, bool swap, PairForm form);
-KernelFn select_duo_kernel(bool crc, int item, bool swap);
-KernelFn select_il_kernel(bool crc, int item, bool swap, bool aff);
-MultiFn select_il_multi_kernel(bool crc, int item, bool swap, bool aff);  // k_decode_il_multi, the same forms
-KernelFn select_ilw_kernel(int item, bool swap, IlwForm form, bool lmr, bool aff);
-KernelFn select_ilh_kernel(int item, bool swap, bool lb, bool aff);
+KernelFn select_rows_kernel(bool crc, int item, int swap, int k);
+KernelFn select_pair_kernel(bool crc, int item, int swap, PairForm form);
+KernelFn select_duo_kernel(bool crc, int item, int swap);
+KernelFn select_il_kernel(bool crc, int item, int swap, bool aff);
+MultiFn select_il_multi_kernel(bool crc, int item, int swap, bool aff);  // k_decode_il_multi, the same forms
+KernelFn select_ilw_kernel(int item, int swap, IlwForm form, bool lmr, bool aff);
+KernelFn select_ilh_kernel(int item, int swap, bool lb, bool aff);
 #if ZHIP_TUNING
-KernelFn select_il_kernel_lean(bool crc, int item, bool swap);
-KernelFn select_il_kernel_tuned(bool crc, int item, bool swap);
-KernelFn select_il_kernel_arm(bool crc, int item, bool swap, int arm);
-KernelFn select_il_kernel_cf(bool crc, int item, bool swap);
-KernelFn select_il_kernel_regmul(bool crc, int item, bool swap, bool occ6);
-KernelFn select_xw_kernel(bool crc, int item, bool swap);
-KernelFn select_ilq_kernel(int item, bool swap, int nq, bool glds);
-KernelFn select_ilc_kernel(int item, bool swap);
-KernelFn select_ilp_kernel(int item, bool swap);
+KernelFn select_il_kernel_lean(bool crc, int item, int swap);
+KernelFn select_il_kernel_tuned(bool crc, int item, int swap);
+KernelFn select_il_kernel_arm(bool crc, int item, int swap, int arm);
+KernelFn select_il_kernel_cf(bool crc, int item, int swap);
+KernelFn select_il_kernel_regmul(bool crc, int item, int swap, bool occ6);
+KernelFn select_xw_kernel(bool crc, int item, int swap);
+KernelFn select_ilq_kernel(int item, int swap, int nq, bool glds);
+KernelFn select_ilc_kernel(int item, int swap);
+KernelFn select_ilp_kernel(int item, int swap);
 #endif
 // decode_tile.hip
 #if ZHIP_TUNING
-KernelFn select_tile4f_kernel(int item, bool swap);
+KernelFn select_tile4f_kernel(int item, int swap);
 #endif
-KernelFn select_tile4_kernel(bool crc, int item, bool swap);
-KernelFn select_tile4w_kernel(int item, bool swap);
-KernelFn select_tile2w_kernel(int item, bool swap, Tile2wForm form);
-KernelFn select_tilegw_kernel(int item, bool swap, bool defer, TilegwForm form);
-KernelFn select_tileg_kernel(bool crc, int item, bool swap, bool defer);
-EncodeFn select_encode_tile4_kernel(bool crc, int item, bool swap, bool two);
-EncodeFn select_encode_tile_kernel(bool crc, int item, bool swap);
-EncodeFn select_encode_tileg_kernel(bool crc, int item, bool swap, EncTilegForm form);
+KernelFn select_tile4_kernel(bool crc, int item, int swap);
+KernelFn select_tile4w_kernel(int item, int swap);
+KernelFn select_tile2w_kernel(int item, int swap, Tile2wForm form);
+KernelFn select_tilegw_kernel(int item, int swap, bool defer, TilegwForm form);
+KernelFn select_tileg_kernel(bool crc, int item, int swap, bool defer);
+EncodeFn select_encode_tile4_kernel(bool crc, int item, int swap, bool two);
+EncodeFn select_encode_tile_kernel(bool crc, int item, int swap);
+EncodeFn select_encode_tileg_kernel(bool crc, int item, int swap, EncTilegForm form);
 
 }  // namespace zhip
 

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/zarrhip.h"
+#include "zhip_fill_eq.h"
 #include "zhip_gf2.h"
 
 namespace zhip {
@@ -46,14 +47,14 @@ ZHIP_HD uint64_t vt_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
 ZHIP_HD uint64_t vt_bits(double f) { return __builtin_bit_cast(uint64_t, f); }
 
 ZHIP_HD bool vt_is_nan(uint32_t dt, uint64_t x) {
-    if (dt == ZHIP_VT_F32) return ((uint32_t)x & 0x7FFFFFFFu) > 0x7F800000u;
-    if (dt == ZHIP_VT_F64) return (x & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull;
+    if (dt == ZHIP_VT_F32) return bits_nan<4>(x);
+    if (dt == ZHIP_VT_F64) return bits_nan<8>(x);
     return false;
 }
 
 // NDBuffer.all_equal against the array fill (buffer/core.py:534-558), the rule
-// encode.hip's item_eq_fill and decode_tile.hip's block_eq_fill_e state for
-// the encode kernels: bitwise, except that any NaN equals a NaN fill.
+// of zhip_fill_eq.h over a value type code (integers, float32, float64):
+// bitwise, except that any NaN equals a NaN fill.
 ZHIP_HD bool value_eq_fill(const zhip_value_op& op, uint64_t x) {
     const uint64_t m = vt_mask(op.array_dt);
     return (x & m) == (op.fill & m) || (op.fill_nan && vt_is_nan(op.array_dt, x));

@@ -8,7 +8,7 @@ Drop-in for zarr-python's CodecPipeline (src/zarr/abc/codec.py:315-508): see
 """
 
 from .array import Array, ArrayMetadata, ChunkNotFoundError
-from .buffer import Buffer, BufferPrototype, NDBuffer, buffer_prototype
+from .buffer import Buffer, BufferPrototype, NDBuffer, UnsupportedDTypeError, buffer_prototype
 from .codecs import BytesCodec, Crc32cCodec, ShardingCodec, TransposeCodec
 from .pipeline import DecodeProgram, HipCodecPipeline, ReadGraph
 from .spec import ArrayConfig, ArraySpec, GetResult
@@ -19,4 +19,5 @@ __all__ = [
     "ChunkNotFoundError", "NDBuffer", "buffer_prototype",
     "Crc32cCodec", "DecodeProgram", "DeviceStore", "GetResult", "HipCodecPipeline", "LocalStore",
     "MemoryStore", "PinnedMemoryStore", "ReadGraph", "ShardingCodec", "StorePath", "TransposeCodec",
+    "UnsupportedDTypeError",
 ]

@@ -26,6 +26,7 @@ LF_SHARDED = 4
 LF_INDEX_START = 8
 LF_NO_WRITE = 16
 LF_FLOAT = 32
+LF_COMPLEX = 64  # 8-byte items of two float32 (complex64)
 
 CF_MISSING = 1
 
@@ -373,6 +374,8 @@ def lib():
     L.zhip_axis_fill.restype = ctypes.c_int
     L.zhip_emulate_axis.argtypes = [vp, vp, u64, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, u64]
     L.zhip_emulate_axis.restype = ctypes.c_int
+    L.zhip_emulate_fill_eq.argtypes = [u32, u32, vp, vp, u64, vp, vp]
+    L.zhip_emulate_fill_eq.restype = ctypes.c_int
     if L.zhip_abi_version() != 1:
         raise NativeError("libzarrhip ABI version mismatch")
     if L.zhip_tuning_build() and not _override_allowed():

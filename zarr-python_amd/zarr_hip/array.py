@@ -28,7 +28,27 @@ from .spec import ArrayConfig, ArraySpec
 from .store import DeviceStore, StorePath
 
 
+def _float_to_json(f: float):
+    """float_to_json_v3 (src/zarr/core/dtype/npy/common.py:256-293)."""
+    if math.isnan(f):
+        return "NaN"
+    if math.isinf(f):
+        return "Infinity" if f > 0 else "-Infinity"
+    return f
+
+
 def _fill_from_json(v, dtype: np.dtype):
+    if dtype.kind == "c":
+        # [re, im], each a number or "NaN" / "Infinity" / "-Infinity"
+        # (complex_float_from_json_v3, common.py:351-365); the components are
+        # set one by one: complex(re, im) arithmetic is not involved, so a
+        # -0.0 or NaN component keeps its sign
+        if not isinstance(v, (list, tuple)) or len(v) != 2:
+            raise ValueError(f"a complex fill value is [real, imag] in zarr.json, got {v!r}")
+        a = np.zeros((), dtype=dtype)
+        a.real = float(v[0])
+        a.imag = float(v[1])
+        return a[()]
     if isinstance(v, str):
         return np.array(float(v), dtype=dtype)[()]
     return np.array(v, dtype=dtype)[()]
@@ -36,13 +56,11 @@ def _fill_from_json(v, dtype: np.dtype):
 
 def _fill_to_json(v, dtype: np.dtype):
     a = np.asarray(v, dtype=dtype)
+    if dtype.kind == "c":
+        # complex_float_to_json_v3 (common.py:296-312)
+        return [_float_to_json(float(a.real)), _float_to_json(float(a.imag))]
     if dtype.kind == "f":
-        f = float(a)
-        if math.isnan(f):
-            return "NaN"
-        if math.isinf(f):
-            return "Infinity" if f > 0 else "-Infinity"
-        return f
+        return _float_to_json(float(a))
     if dtype.kind == "b":
         return bool(a)
     return int(a)
@@ -139,6 +157,7 @@ class Array:
     def __init__(self, store_path: StorePath, metadata: ArrayMetadata,
                  config: ArrayConfig = ArrayConfig()):
         self.store_path = store_path
+        buffer.require_device_dtype(metadata.dtype)
         self.metadata = metadata
         self.config = config
         # (rectilinear grids: the pipeline is evolved with the placeholder
@@ -159,6 +178,7 @@ class Array:
                inner_codecs=None, index_location="end", path: str = "",
                config: ArrayConfig = ArrayConfig()) -> "Array":
         dtype = np.dtype(dtype)
+        buffer.require_device_dtype(dtype)  # (refused by name before zarr.json is written)
         if codecs is None:
             codecs = (BytesCodec(endian="little" if dtype.itemsize > 1 else None),)
         codecs = tuple(parse_codecs(codecs))

@@ -23,6 +23,41 @@ import numpy as np
 
 _MAP = None
 
+# what the device path serves: items of 1, 2, 4 or 8 bytes the kernels move
+# whole (either byte order), complex64 as two float32 (ZHIP_LF_COMPLEX)
+DEVICE_DTYPES = ("bool", "int8", "uint8", "int16", "uint16", "int32", "uint32", "int64", "uint64",
+                 "float16", "float32", "float64", "complex64")
+
+
+_ADMITTED: dict = {}
+
+
+class UnsupportedDTypeError(TypeError):
+    """The array's dtype has no device path (complex128, datetimes, strings,
+    structured types, ...).  Raised on the host, before anything is reserved
+    or launched; the message names the dtype."""
+
+
+def require_device_dtype(dtype) -> np.dtype:
+    """The one admission check of the device path (planner.analyze_chain and
+    torch_dtype call it): the native-order dtype, or UnsupportedDTypeError."""
+    if type(dtype) is np.dtype and dtype in _ADMITTED:  # (the boundary asks per call)
+        return _ADMITTED[dtype]
+    from .interop import native_dtype
+
+    try:
+        dt = np.dtype(native_dtype(dtype))
+    except TypeError as e:
+        raise UnsupportedDTypeError(f"dtype {dtype!r} has no device representation") from e
+    nat = dt.newbyteorder("=")
+    if nat.name not in DEVICE_DTYPES or nat != np.dtype(nat.name):
+        raise UnsupportedDTypeError(
+            f"dtype {dt.name} (item size {dt.itemsize}) has no device representation: the device path serves "
+            f"{', '.join(DEVICE_DTYPES)}")
+    if type(dtype) is np.dtype:
+        _ADMITTED[dtype] = nat
+    return nat
+
 
 def torch_dtype(dtype) -> "torch.dtype":
     import torch
@@ -38,12 +73,7 @@ def torch_dtype(dtype) -> "torch.dtype":
             np.dtype("float32"): torch.float32, np.dtype("float64"): torch.float64,
             np.dtype("complex64"): torch.complex64,
         }
-    from .interop import native_dtype
-
-    dt = native_dtype(dtype).newbyteorder("=")
-    if dt not in _MAP:
-        raise TypeError(f"dtype {dt} has no device representation")
-    return _MAP[dt]
+    return _MAP[require_device_dtype(dtype)]
 
 
 def numpy_dtype(td) -> np.dtype:
@@ -347,24 +377,29 @@ class NDBuffer(_NDBufferBase):
         return f"<NDBuffer shape={self.shape} dtype={self.dtype} device={self._data.device}>"
 
     def all_equal(self, other: Any, equal_nan: bool = True) -> bool:
-        """NDBuffer.all_equal (core.py:534-558): bitwise against 0 (so -0.0 and NaN
-        payloads count as non-empty), NaN-equal otherwise when equal_nan."""
+        """NDBuffer.all_equal (core.py:534-558): bitwise against a float 0 (so
+        -0.0 and +0.0 differ), np.array_equal with equal_nan otherwise --
+        integers and bool by their bits (through a signed view of the item
+        size: the unsigned 16/32/64-bit tensors have no comparison kernels),
+        floats and complex64 by value, any NaN item equal to a NaN `other`.
+        The interface's host-facing statement of the rule; the device write
+        path decides emptiness inside the encode kernels (csrc/zhip_fill_eq.h)."""
         import torch
 
         if other is None:
             return False
         t = self._data
-        fv = np.asarray(other, dtype=self.dtype)
-        if np.asarray(other).dtype.kind == "f" and other == 0.0:
-            # bit patterns, so -0.0 and +0.0 differ (core.py:539-547)
-            iv = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]
-            bits = int(fv.reshape(1).view({1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}[
-                fv.itemsize])[0])
-            return bool((t.contiguous().view(iv) == bits).all().item())
-        ref = torch.as_tensor(fv, device=t.device).to(t.dtype)
+        fv = np.asarray(other, dtype=self.dtype).reshape(1)
+        iv = {1: (torch.int8, np.int8), 2: (torch.int16, np.int16), 4: (torch.int32, np.int32),
+              8: (torch.int64, np.int64)}[t.element_size()]
+        if self.dtype.kind in "biu" or (np.asarray(other).dtype.kind == "f" and other == 0.0):
+            bits = int(fv.view(iv[1])[0])
+            tc = t.contiguous()
+            return bool(((tc.view(torch.uint8) if tc.dtype == torch.bool else tc).view(iv[0]) == bits).all().item())
+        ref = torch.from_numpy(fv.copy()).to(t.device).reshape(())
         eq = t == ref
-        if equal_nan and self.dtype.kind in "fc" and bool(np.isnan(fv).all()):
-            eq = eq | torch.isnan(t)
+        if equal_nan and bool(np.isnan(fv).any()):
+            eq = torch.isnan(t)  # NaN-ness must agree item by item; a NaN equals nothing by value
         return bool(eq.all().item())
 
     def fill(self, value: Any) -> None:

@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _native as N
 from . import fancy, staging
+from .buffer import require_device_dtype
 from .codecs import (ShardingCodec, TransposeCodec, evolve_codecs, is_v2_codec, parse_codecs, split_codecs,
                      split_host_tail)
 from .interop import device_tensor, host_array
@@ -1382,6 +1383,14 @@ class HipCodecPipeline:
                              generations=((one[0].arena, one[0].arena.gen),) if one is not None
                              else _generations(batch))
 
+    @staticmethod
+    def _admit(batch_info: list) -> None:
+        """The dtype admission check at the boundary (buffer.require_device_dtype):
+        a batch of an unsupported dtype is refused by name before a twin is
+        allocated, an arena range reserved or anything launched."""
+        if batch_info:
+            require_device_dtype(batch_info[0][1].dtype)
+
     def read_sync(self, batch_info: Iterable, out, drop_axes: tuple = (),
                   max_workers: int = 1) -> tuple[GetResult, ...]:
         """FusedCodecPipeline.read_sync (codec_pipeline.py:1095-1172) on the GPU.
@@ -1397,6 +1406,7 @@ class HipCodecPipeline:
         basic items of such a batch still decode through the path below."""
         if not isinstance(batch_info, list):
             batch_info = list(batch_info)
+        self._admit(batch_info)
         if type(batch_info) is not BasicBatch and fancy.any_fancy(batch_info):
             return fancy.read(self, batch_info, out, drop_axes)
         vs = self._value_split()
@@ -1641,6 +1651,7 @@ class HipCodecPipeline:
         torch = _torch()
         if not isinstance(batch_info, list):
             batch_info = list(batch_info)
+        self._admit(batch_info)
         if type(batch_info) is not BasicBatch and fancy.any_fancy(batch_info):  # orthogonal / coordinate / mask
             return fancy.write(self, batch_info, value, drop_axes, partial_encode)
         vs = self._value_split()

@@ -17,6 +17,7 @@ import struct as _struct
 import numpy as np
 
 from . import _native as N
+from .buffer import require_device_dtype
 from .codecs import BytesCodec, Crc32cCodec, ShardingCodec, TransposeCodec, is_host_codec, split_codecs, \
     split_host_tail
 from .indexing import basic_projections
@@ -42,7 +43,20 @@ class ChainInfo:
     inner_host: tuple = ()
 
 
+def layout_flags(chain: ChainInfo, dtype: np.dtype, encode: bool = False) -> int:
+    """zhip_layout.flags of a fixed-size chain over `dtype`: checksum, byte
+    swap, and the item kind -- complex64 (ZHIP_LF_COMPLEX: the swap reverses
+    each float32 component, the encode compares with the fill by the complex
+    rule) and, for an encode, IEEE floats (ZHIP_LF_FLOAT: any NaN equals a NaN
+    fill)."""
+    return (N.LF_CRC if chain.crc else 0) | (N.LF_SWAP if chain.swap else 0) | \
+        (N.LF_COMPLEX if dtype.kind == "c" else 0) | (N.LF_FLOAT if encode and dtype.kind == "f" else 0)
+
+
 def analyze_chain(codecs, spec: ArraySpec) -> ChainInfo:
+    # the admission check of every read, write, prepare_read and fancy path:
+    # an unsupported dtype is refused here, by name, before any reservation
+    require_device_dtype(spec.dtype)
     aa, ab, bb = split_codecs(codecs)
     if any(is_host_codec(c) for c in bb):
         raise NotImplementedError("the host stage of this chain must be split off first "
@@ -286,8 +300,7 @@ def plan_encode(chain: ChainInfo, spec: ArraySpec, items: list, arr_strides_byte
     shape_st = [spec.shape[p] for p in perm]
     ost = np.asarray(arr_strides_bytes, np.int64)
     ost_st = [int(ost[p]) for p in perm]
-    flags = (N.LF_CRC if chain.crc else 0) | (N.LF_SWAP if chain.swap else 0) | \
-        (N.LF_FLOAT if spec.dtype.kind == "f" else 0)
+    flags = layout_flags(chain, spec.dtype, encode=True)
     layout = _make_layout(shape_st, itemsize, ost_st, flags, spec.fill_bytes())
     n = len(items)
     chunks = np.zeros(n, CHUNK_DT)
@@ -342,7 +355,7 @@ def plan_decode(chain: ChainInfo, spec: ArraySpec, items: list, out_strides_byte
         perm = chain.perm
         shape_st = [spec.shape[p] for p in perm]
         ost_st = [ost_dec[p] for p in perm]
-        flags = (N.LF_CRC if chain.crc else 0) | (N.LF_SWAP if chain.swap else 0)
+        flags = layout_flags(chain, spec.dtype)
         layout = _make_layout(shape_st, itemsize, ost_st, flags, fill)
         n = len(items)
         chunks = np.zeros(n, CHUNK_DT)
@@ -390,7 +403,7 @@ def plan_decode(chain: ChainInfo, spec: ArraySpec, items: list, out_strides_byte
     shape_st = [inner_shape[p] for p in perm]
     ost_st = [ost_dec[p] for p in perm]
     index_size = sh.shard_index_size(n_inner)
-    flags = (N.LF_CRC if inner.crc else 0) | (N.LF_SWAP if inner.swap else 0)
+    flags = layout_flags(inner, spec.dtype)
     if resolved is None:
         flags |= N.LF_SHARDED | (N.LF_INDEX_START if sh.index_location == "start" else 0)
         layout = _make_layout(shape_st, itemsize, ost_st, flags, fill, n_inner, index_size)
@@ -499,7 +512,7 @@ def _native_ctx(chain: ChainInfo, spec: ArraySpec, ost_dec, fill, staged: bool =
     g["perm"][0, :ndim] = perm
     g["shape"][0, :ndim] = shape
     g["ost"][0, :ndim] = ost_dec
-    flags = (N.LF_CRC if inner.crc else 0) | (N.LF_SWAP if inner.swap else 0)
+    flags = layout_flags(inner, spec.dtype)
     n_inner, index_layout = 1, None
     if sh is not None:
         inner_shape = sh.chunk_shape
