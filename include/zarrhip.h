@@ -495,6 +495,11 @@ int zhip_set_tuning(int key, int value);
  * "k_decode_pair", "k_decode_lead", "k_encode_il", ...): a diagnostic for
  * labels and tests; not synchronised across threads. */
 const char *zhip_last_kernel(void);
+/* Workgroups of that launch (its grid).  The persistent kernels ("k_decode",
+ * "k_decode_rows", "k_decode_tile", "k_encode") launch min(units, resident
+ * workgroups), which the call's arguments do not determine; for every other
+ * kernel the grid follows from them.  Same caveats as zhip_last_kernel(). */
+uint32_t zhip_last_grid(void);
 
 /* Diagnostics: with ablation bit 1024 set, k_decode_pair records per-workgroup
  * phase timestamps (s_memrealtime, 100 MHz) for the first 8192 workgroups of

@@ -482,6 +482,7 @@ static KernelFn select_tile_kernel(bool crc, int item, int swap) {
 // name of the kernel the last launch_decode chose (zhip_last_kernel: bench
 // labels and tests; the selection depends on layout, plan and tuning bits)
 const char* g_last_kernel = "";
+uint32_t g_last_grid = 0;
 #if ZHIP_TUNING
 // Overhead probes (arms 28-30; results invalid): the launch of a decode-shaped
 // grid with the decode's kernel arguments and nothing else (28), plus the
@@ -926,4 +927,5 @@ int launch_decode(const DecodeParams& p, hipStream_t stream, int max_grid) {
 }  // namespace zhip
 
 extern "C" const char* zhip_last_kernel(void) { return zhip::g_last_kernel; }
+extern "C" uint32_t zhip_last_grid(void) { return zhip::g_last_grid; }
 extern "C" uint64_t zhip_launch_count(void) { return zhip::g_launch_count; }

@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const uint4 f = make_uint4(p.fill[0], p.fill[1], p.fill[2], p.fill[3]);
     PendingU pend;
     pend.valid = 0;
-    uint32_t acc = 0, run_bits = 0, parity = 0;
+    uint32_t acc = 0, run_bits = 0, run_len = 0, parity = 0;
     uint32_t first = 1u;
     ub = ua;
     for (uint32_t q = q0;;) {
@@ -340,6 +340,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                     }
                 }
                 run_bits |= 1u << (ua.sidx & 31u);
+                ++run_len;
                 if (run_end) {
                     uint32_t v = (p.tune & kTuneNoLaneMul) ? acc : lanemul(s_mul, s_r4, t, acc);
                     v = wave_xor(v);
@@ -364,9 +365,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                             pend.V = V;
                             pend.valid = 1;
                         } else {
-                            // > 32 units per chunk: xor, then count arrivals
+                            // > 32 units per chunk: xor, then count arrivals (counted, not
+                            // the population of run_bits: a run of more than 32 units sets
+                            // some bit of the mask twice)
                             uint32_t raw = 0, last = 0;
-                            const uint32_t n_run = __builtin_popcount(run_bits);
+                            const uint32_t n_run = run_len;
                             if (t == 0) {
                                 uint32_t* accw = p.ws + 4ull * ua.c;
                                 const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED,
@@ -392,6 +395,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                     parity ^= 1u;
                     acc = 0;
                     run_bits = 0;
+                    run_len = 0;
                 }
             } else {
                 if (ua.sidx == 0 && t == 0) {

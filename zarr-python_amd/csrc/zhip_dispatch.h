@@ -75,6 +75,7 @@ int fire(void (*fn)(const P), const char* name, uint32_t grid, uint32_t block, c
     if (!fn) return ZHIP_E_UNSUPPORTED;
     if (grid == 0) return ZHIP_OK;
     g_last_kernel = name;
+    g_last_grid = grid;
     ++g_launch_count;
     hipLaunchKernelGGL(fn, dim3(grid), dim3(block), 0, stream, params);
     return hipGetLastError() == hipSuccess ? ZHIP_OK : ZHIP_E_HIP;

@@ -54,6 +54,7 @@ constexpr int kPairTabWords = 6144;
 // / k_decode_tilegw): A_D's four 256-entry byte tables, then the A4 fold tables
 constexpr int kByteTabWords = 2048;
 extern const char* g_last_kernel;  // zhip_last_kernel: the kernel the last decode / mapped encode launched
+extern uint32_t g_last_grid;       // zhip_last_grid: that launch's workgroups (fire)
 constexpr uint32_t kIlwMaxUnits = 512;  // k_decode_ilw (512 lanes) for grids of at most 2 units per CU
 constexpr int kIlBasisWords = 64;  // T1 / T2 / T3 bases (11 + 11 + 10, padded to 32), A4 bases (4 x 8)
 
