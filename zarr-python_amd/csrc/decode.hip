@@ -37,6 +37,7 @@
 #include "zhip_dispatch.h"
 #include "zhip_device.h"
 #include "zhip_decode_common.h"
+#include "zhip_arrival.h"
 
 namespace zhip {
 
@@ -63,9 +64,9 @@ __global__ __launch_bounds__(kThreads) void k_decode(const DecodeParams p) {
         kth = p.kthread[t];
     }
     const uint32_t expected = p.g.nbytes + (CRC ? 4u : 0u);
-    // one 64-bit arrival word per chunk: high half = bitmask of arrived units, low = xor
+    // the mask form up to 32 units per chunk (zhip_arrival.h)
     const bool one_atomic = p.nseg <= 32 && !(p.tune & (kTuneAcqRel | kTuneNoTicket));
-    const uint64_t full = p.nseg >= 32 ? 0xFFFFFFFFull : ((1ull << p.nseg) - 1ull);
+    const uint64_t full = mask_of(p.nseg);
     Pending pend;
     pend.valid = 0;
 
@@ -152,14 +153,16 @@ __global__ __launch_bounds__(kThreads) void k_decode(const DecodeParams p) {
                         if (one_atomic) {
                             retire(p, pend, full);  // the previous run's arrival has returned by now
                             uint64_t* w = reinterpret_cast<uint64_t*>(p.ws) + 2ull * ua.c;
-                            pend.prev = __hip_atomic_fetch_xor(w, ((uint64_t)run_bits << 32) | V,
-                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            pend.prev = mask_issue(w, run_bits, V);
                             pend.stored = stored;
                             pend.c = ua.c;
                             pend.bits = run_bits;
                             pend.V = V;
                             pend.valid = 1;
                         } else {
+                            // the counted form (arrive_count, zhip_arrival.h) written out: the two
+                            // tuning-only forms (an acq_rel ticket in place of the wait; no ticket,
+                            // no verdict) share its steps
                             uint32_t* accw = p.ws + 4ull * ua.c;
                             uint32_t tk;
                             if (p.tune & kTuneAcqRel) {
@@ -167,8 +170,6 @@ __global__ __launch_bounds__(kThreads) void k_decode(const DecodeParams p) {
                                 tk = __hip_atomic_fetch_add(accw + 2, run_len, __ATOMIC_ACQ_REL,
                                                             __HIP_MEMORY_SCOPE_AGENT);
                             } else {
-                                // the xor must be performed at the device-coherent point
-                                // before the count is drawn: wait for its return first
                                 const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED,
                                                                              __HIP_MEMORY_SCOPE_AGENT);
                                 asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
@@ -267,7 +268,8 @@ __global__ __launch_bounds__(kThreads) void k_decode_tile(const DecodeParams p) 
     for (uint32_t q = q0; q < q1; ++q) {
         const uint32_t c = q / p.t_per_chunk;
         const uint32_t ti = q - c * p.t_per_chunk;
-        // chunk source (as resolve_unit)
+        // chunk source (resolve_unit's rule over vector loads; a shared helper changes that
+        // function's scalar code in every kernel that resolves units)
         const zhip_chunk ch = p.chunks[c];
         uint32_t mode = ZHIP_ST_OK;
         uint64_t base = ch.src;
@@ -399,18 +401,9 @@ __global__ __launch_bounds__(kThreads) void k_decode_tile(const DecodeParams p) 
                     ++run_len;
                     const bool run_end = (q + 1 >= q1) || ((q + 1) / p.t_per_chunk != c);
                     if (run_end) {
-                        uint32_t* accw = p.ws + 4ull * c;
-                        const uint32_t prev =
-                            __hip_atomic_fetch_xor(accw, runV, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-                        const uint32_t tk =
-                            __hip_atomic_fetch_add(accw + 2, run_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (tk + run_len == p.t_per_chunk) {
-                            const uint32_t raw =
-                                __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_store(accw + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        arrive_count(p.ws + 4ull * c, runV, run_len, p.t_per_chunk, [&](uint32_t raw) {
                             finalize_chunk(p, c, load_trailer(cp, p.g.nbytes), raw);
-                        }
+                        });
                         runV = 0;
                         run_len = 0;
                     }

@@ -24,6 +24,7 @@
 #include "zhip_dispatch.h"
 #include "zhip_device.h"
 #include "zhip_decode_common.h"
+#include "zhip_arrival.h"
 
 namespace zhip {
 
@@ -181,44 +182,6 @@ __device__ __forceinline__ uint32_t lanemul(const uint32_t* s_mul, const uint32_
     return p;
 }
 
-// Wave-uniform multiply (scalar ALU): both operands are read from lane 0.
-__device__ __forceinline__ uint32_t gf_mul_uniform(uint32_t a, uint32_t b) {
-    return gf_mul(__builtin_amdgcn_readfirstlane(a), __builtin_amdgcn_readfirstlane(b));
-}
-
-// The arrival protocol of k_decode, executed wave-uniformly by wave 0 so the
-// GF(2) work runs on the scalar unit; only lane 0 touches memory.
-struct PendingU {
-    uint64_t prev;  // lane 0: returned 64-bit arrival word (consumed one run later)
-    uint32_t stored, c, bits, V, valid;
-};
-
-__device__ __forceinline__ void finalize_uniform(const DecodeParams& p, uint32_t c, uint32_t stored, uint32_t raw,
-                                                 int t, bool scaled = false) {
-    const uint32_t computed = ~((scaled ? raw : gf_mul_uniform(raw, p.c_inv)) ^ p.c3);
-    const uint32_t code = computed == stored ? ZHIP_ST_OK : ZHIP_ST_CRC_MISMATCH;
-    if (t == 0) {
-        zhip_status st = {code, stored, computed, 0u};
-        p.status[c] = st;
-        if (code != ZHIP_ST_OK) atomicOr(p.errflag, 1u << code);
-    }
-}
-
-__device__ __forceinline__ void retire_uniform(const DecodeParams& p, PendingU& q, uint64_t full, int t,
-                                               bool scaled = false) {
-    if (!q.valid) return;
-    q.valid = 0;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)q.prev);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(q.prev >> 32));
-    if ((uint64_t)(hi ^ q.bits) == full) {
-        if (t == 0) {
-            uint64_t* w = reinterpret_cast<uint64_t*>(p.ws) + 2ull * q.c;
-            __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        finalize_uniform(p, q.c, q.stored, lo ^ q.V, t, scaled);
-    }
-}
-
 }  // namespace
 
 template <bool CRC, int ITEM, int SWAP, int K = 8>
@@ -278,7 +241,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const uint32_t lane_col = (16u * (uint32_t)t) & ((1u << p.row_shift) - 1u);
     const int64_t lane_off = (int64_t)lane_row * p.r_oy + (int64_t)lane_col;
     const bool one_atomic = p.nseg <= 32;
-    const uint64_t full = p.nseg >= 32 ? 0xFFFFFFFFull : ((1ull << p.nseg) - 1ull);
+    const uint64_t full = mask_of(p.nseg);
     const uint4 f = make_uint4(p.fill[0], p.fill[1], p.fill[2], p.fill[3]);
     PendingU pend;
     pend.valid = 0;
@@ -356,8 +319,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                             retire_uniform(p, pend, full, t);  // the previous run's arrival returned by now
                             if (t == 0) {
                                 uint64_t* w = reinterpret_cast<uint64_t*>(p.ws) + 2ull * ua.c;
-                                pend.prev = __hip_atomic_fetch_xor(w, ((uint64_t)run_bits << 32) | V,
-                                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                pend.prev = mask_issue(w, run_bits, V);
                             }
                             pend.stored = __builtin_amdgcn_readfirstlane(stored);
                             pend.c = ua.c;
@@ -365,27 +327,16 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                             pend.V = V;
                             pend.valid = 1;
                         } else {
-                            // > 32 units per chunk: xor, then count arrivals (counted, not
-                            // the population of run_bits: a run of more than 32 units sets
-                            // some bit of the mask twice)
+                            // > 32 units per chunk: the counted form (run_len, not the
+                            // population of run_bits: a run of more than 32 units sets some
+                            // bit of the mask twice)
                             uint32_t raw = 0, last = 0;
                             const uint32_t n_run = run_len;
                             if (t == 0) {
-                                uint32_t* accw = p.ws + 4ull * ua.c;
-                                const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED,
-                                                                             __HIP_MEMORY_SCOPE_AGENT);
-                                asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-                                const uint32_t tk = __hip_atomic_fetch_add(accw + 2, n_run, __ATOMIC_RELAXED,
-                                                                           __HIP_MEMORY_SCOPE_AGENT);
-                                if (tk + n_run == p.nseg) {
-                                    raw = __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    // consume the returned value here (rare path): a register with a
-                    // load still pending would make every later write to it wait
-                    // for the wave's stores too
-                    asm volatile("s_waitcnt vmcnt(0)" ::"v"(raw) : "memory");
-                                    __hip_atomic_store(accw + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                arrive_count<true>(p.ws + 4ull * ua.c, V, n_run, p.nseg, [&](uint32_t r) {
+                                    raw = r;
                                     last = 1;
-                                }
+                                });
                             }
                             if (__builtin_amdgcn_readfirstlane(last))
                                 finalize_uniform(p, ua.c, __builtin_amdgcn_readfirstlane(stored),
@@ -498,17 +449,7 @@ __device__ __forceinline__ void verify_index_pair(const DecodeParams& p, uint32_
     __syncthreads();  // red may still be read from a previous index
     if (active && (t & 63) == 0) red[t >> 6] = v;
     __syncthreads();
-    if (active && t == 0) {
-        zhip_status st = {ZHIP_ST_LENGTH_MISMATCH, 0u, 0u, 0u};
-        if (ok) {
-            const uint32_t V = red[0] ^ red[1] ^ red[2] ^ red[3];
-            st.stored = load_trailer(cp, p.idx_nbytes);
-            st.computed = ~(gf_mul(V, p.idx_c_inv) ^ p.idx_c3);
-            st.code = st.computed == st.stored ? ZHIP_ST_OK : ZHIP_ST_CRC_MISMATCH;
-        }
-        p.idx_status[j] = st;
-        if (st.code != ZHIP_ST_OK) atomicOr(p.errflag, 1u << st.code);
-    }
+    if (active && t == 0) index_verdict(p, j, ok, cp, red);
 }
 
 // The K = 8 steps of one unit in the row map (zhip_rows_map): 64 bytes, one
@@ -548,50 +489,29 @@ __device__ __forceinline__ void store_unit_rows(const DecodeParams& p, const Uni
     }
 }
 
-// Publication of a run's reduced contribution V by wave 0 (wave-uniform, lane 0
-// touches memory): one 64-bit atomic (contribution | arrival bits) when a chunk
-// has <= 32 units, else xor + arrival count; the arrival that completes the
-// chunk compares with the trailer.
+// Publication of a run's reduced contribution V by wave 0 (publish_bits,
+// zhip_arrival.h; run_bits has one bit per unit of the run).
 __device__ __forceinline__ void publish_run(const DecodeParams& p, const Unit& U, uint32_t V, uint32_t run_bits,
                                             uint32_t stored, int t) {
     if (p.tune & kTuneNoTicket) {  // ablation: no publication / last-arriver
         if (t == 0 && V == 0x9E3779B9u) p.status[U.c].aux = V;
     } else if (p.nseg <= 32) {
-        const uint64_t full = p.nseg >= 32 ? 0xFFFFFFFFull : ((1ull << p.nseg) - 1ull);
-        uint64_t prev = 0;
+        // publish_bits' mask form spelled through PendingU (the word's address
+        // formed by the issuing lane alone): k_decode_pair's code depends on it
+        PendingU q;
+        q.prev = 0;
         if (t == 0) {
             uint64_t* w = reinterpret_cast<uint64_t*>(p.ws) + 2ull * U.c;
-            prev = __hip_atomic_fetch_xor(w, ((uint64_t)run_bits << 32) | V, __ATOMIC_RELAXED,
-                                          __HIP_MEMORY_SCOPE_AGENT);
+            q.prev = mask_issue(w, run_bits, V);
         }
-        PendingU q;
-        q.prev = prev;
         q.stored = stored;
         q.c = U.c;
         q.bits = run_bits;
         q.V = V;
         q.valid = 1;
-        retire_uniform(p, q, full, t, true);
-    } else {  // > 32 units per chunk: xor, then count arrivals
-        uint32_t raw = 0, last = 0;
-        const uint32_t n_run = __builtin_popcount(run_bits);
-        if (t == 0) {
-            uint32_t* accw = p.ws + 4ull * U.c;
-            const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-            const uint32_t tk = __hip_atomic_fetch_add(accw + 2, n_run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk + n_run == p.nseg) {
-                raw = __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                // consume the returned value here (rare path): a register with a
-                // load still pending would make every later write to it wait
-                // for the wave's stores too
-                asm volatile("s_waitcnt vmcnt(0)" ::"v"(raw) : "memory");
-                __hip_atomic_store(accw + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                last = 1;
-            }
-        }
-        if (__builtin_amdgcn_readfirstlane(last))
-            finalize_uniform(p, U.c, stored, __builtin_amdgcn_readfirstlane(raw), t, true);
+        retire_uniform(p, q, mask_of(p.nseg), t, true);
+    } else {
+        publish_bits(p, U.c, run_bits, __builtin_popcount(run_bits), p.nseg, V, stored, t);
     }
 }
 
@@ -1230,35 +1150,7 @@ __global__ __launch_bounds__(2 * kThreads) __attribute__((amdgpu_waves_per_eu(8,
 // >= kPubLine workspace words per chunk for CRC layouts).
 __device__ __forceinline__ void publish_il(const DecodeParams& p, uint32_t c, uint32_t r, uint32_t wpc, uint32_t V,
                                            uint32_t stored, int t, uint32_t wstride = 2u) {
-    if (wpc <= 32u) {
-        const uint64_t full = wpc >= 32u ? 0xFFFFFFFFull : ((1ull << wpc) - 1ull);
-        const uint64_t bits = 1ull << r;
-        uint64_t prev = 0;
-        uint64_t* const w = reinterpret_cast<uint64_t*>(p.ws) + (uint64_t)wstride * c;
-        if (t == 0) prev = __hip_atomic_fetch_xor(w, (bits << 32) | V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)prev);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(prev >> 32));
-        if ((uint64_t)(hi ^ (uint32_t)bits) == full) {
-            if (t == 0) __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            finalize_uniform(p, c, stored, lo ^ V, t, true);
-        }
-    } else {  // more than 32 workgroups per chunk: xor, then count arrivals
-        uint32_t raw = 0, last = 0;
-        if (t == 0) {
-            uint32_t* accw = p.ws + 4ull * c;
-            const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-            const uint32_t tk = __hip_atomic_fetch_add(accw + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk + 1u == wpc) {
-                raw = __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::"v"(raw) : "memory");
-                __hip_atomic_store(accw + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                last = 1;
-            }
-        }
-        if (__builtin_amdgcn_readfirstlane(last))
-            finalize_uniform(p, c, stored, __builtin_amdgcn_readfirstlane(raw), t, true);
-    }
+    publish_bits(p, c, 1ull << r, 1u, wpc, V, stored, t, wstride);
 }
 
 // publish_il through two subwords of 16 arrivals on lines of their own and a
@@ -1688,9 +1580,7 @@ __global__ void k_dv_check(const zhip_dv_ref* refs) {
             const uint32_t w = R.workspace[4ull * c + 2u * b];
             if (w != 0u) {
                 const uint32_t st = R.workspace[4ull * c + 2u * b + 1u];
-                zhip_status s = {ZHIP_ST_CRC_MISMATCH, st, w ^ st, 0u};
-                R.status[c] = s;
-                atomicOr(R.errflag, 1u << ZHIP_ST_CRC_MISMATCH);
+                report_mismatch(R.status, R.errflag, c, st, w);
                 R.workspace[4ull * c + 2u * b] = 0u;
             }
         }
@@ -1759,35 +1649,7 @@ __device__ __forceinline__ void glds16(const void* g, uint32_t lds) {
 // publish_il for a workgroup carrying several arrival bits of chunk c
 __device__ __forceinline__ void publish_ilq(const DecodeParams& p, uint32_t c, uint32_t r0, uint32_t nq, uint32_t wpc,
                                             uint32_t V, uint32_t stored, int t) {
-    if (wpc <= 32u) {
-        const uint64_t full = wpc >= 32u ? 0xFFFFFFFFull : ((1ull << wpc) - 1ull);
-        const uint32_t bits = ((1u << nq) - 1u) << r0;
-        uint64_t prev = 0;
-        uint64_t* const w = reinterpret_cast<uint64_t*>(p.ws) + (uint64_t)(kPubLine / 2u) * c;
-        if (t == 0) prev = __hip_atomic_fetch_xor(w, ((uint64_t)bits << 32) | V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)prev);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(prev >> 32));
-        if ((uint64_t)(hi ^ bits) == full) {
-            if (t == 0) __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            finalize_uniform(p, c, stored, lo ^ V, t, true);
-        }
-    } else {  // more than 32 units per chunk: xor, then count arrivals
-        uint32_t raw = 0, last = 0;
-        if (t == 0) {
-            uint32_t* accw = p.ws + 4ull * c;
-            const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-            const uint32_t tk = __hip_atomic_fetch_add(accw + 2, nq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk + nq == wpc) {
-                raw = __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::"v"(raw) : "memory");
-                __hip_atomic_store(accw + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                last = 1;
-            }
-        }
-        if (__builtin_amdgcn_readfirstlane(last))
-            finalize_uniform(p, c, stored, __builtin_amdgcn_readfirstlane(raw), t, true);
-    }
+    publish_bits(p, c, ((1u << nq) - 1u) << r0, nq, wpc, V, stored, t, kPubLine / 2u);
 }
 
 template <int ITEM, int SWAP, int NQ, bool GLDS>
@@ -2170,7 +2032,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
     stamp(p, g, t, 3);
     // 5. the unit as resolve_unit sees it (zhip_decode_common.h), from the
-    //    vector-loaded entry
+    //    vector-loaded entry (a copy: splitting resolve_unit to share the rule
+    //    changes its scalar code in every kernel that resolves units)
     uint32_t mode = ch_missing ? (uint32_t)ZHIP_ST_MISSING : (uint32_t)ZHIP_ST_OK;
     uint64_t base = ch.src;
     if (has && !ch_missing) {
@@ -2344,20 +2207,20 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                 const uint32_t n_h = h2 ? wpc - 32u : 32u;
                 const uint64_t bit = 1ull << (u & 31u);
                 uint64_t prev = 0;
-                if (t == 0) prev = __hip_atomic_fetch_xor(w + h2, (bit << 32) | V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (t == 0) prev = mask_issue(w + h2, bit, V);
                 const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)prev);
                 const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(prev >> 32));
                 const uint64_t fullh = n_h >= 32u ? 0xFFFFFFFFull : ((1ull << n_h) - 1ull);
-                if ((uint64_t)(hi ^ (uint32_t)bit) == fullh) {
-                    if (t == 0) __hip_atomic_store(w + h2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (mask_full_hi(hi, (uint32_t)bit, fullh)) {
+                    if (t == 0) mask_reset(w + h2);
                     const uint32_t Vh = lo ^ V;
                     const uint64_t hb = 1ull << h2;
                     uint64_t p2 = 0;
-                    if (t == 0) p2 = __hip_atomic_fetch_xor(w + 2, (hb << 32) | Vh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (t == 0) p2 = mask_issue(w + 2, hb, Vh);
                     const uint32_t lo2 = __builtin_amdgcn_readfirstlane((uint32_t)p2);
                     const uint32_t hi2 = __builtin_amdgcn_readfirstlane((uint32_t)(p2 >> 32));
                     if ((hi2 ^ (uint32_t)hb) == 3u) {
-                        if (t == 0) __hip_atomic_store(w + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (t == 0) mask_reset(w + 2);
                         finalize_uniform(p, c, st, lo2 ^ Vh, t, true);
                     }
                 }
@@ -2616,12 +2479,12 @@ __device__ __forceinline__ void publish_xw(const DecodeParams& p, uint32_t c, ui
     const uint64_t bit = 1ull << (r & 31u);
     uint64_t* sw = reinterpret_cast<uint64_t*>(p.ws + 4ull * p.n_chunks) + (uint64_t)c * ns + sg;
     uint64_t prev = 0;
-    if (l == 0) prev = __hip_atomic_fetch_xor(sw, (bit << 32) | V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (l == 0) prev = mask_issue(sw, bit, V);
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)prev);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(prev >> 32));
     const uint64_t full = in_sg >= 32u ? 0xFFFFFFFFull : ((1ull << in_sg) - 1ull);
-    if ((uint64_t)(hi ^ (uint32_t)bit) != full) return;
-    if (l == 0) __hip_atomic_store(sw, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!mask_full_hi(hi, (uint32_t)bit, full)) return;
+    if (l == 0) mask_reset(sw);
     publish_il(p, c, sg, ns, V ^ lo, stored, (int)l);
 }
 

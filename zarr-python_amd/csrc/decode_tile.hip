@@ -26,6 +26,7 @@
 #include "zhip_fill_eq.h"
 #include "zhip_device.h"
 #include "zhip_decode_common.h"
+#include "zhip_arrival.h"
 
 namespace zhip {
 namespace {
@@ -227,6 +228,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             if (PUB == 2) {
                 if (t == 0) dv_publish(p, c, grp == 0, V, __builtin_amdgcn_readfirstlane(stored));
             } else if (t == 0) {
+                // (zhip_arrival.h's mask / counted forms and verdict, written out: through the helpers this
+                // kernel's generated code changes outside the arrival block)
                 if (gpc <= 32) {
                     const uint64_t full = gpc == 32 ? 0xFFFFFFFFull : ((1ull << gpc) - 1ull);
                     const uint64_t bits = 1ull << grp;
@@ -392,34 +395,19 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             uint32_t raw = 0, last_arrival = 0;
             if (t == 0) {
                 if (gpc <= 32) {
-                    const uint64_t full = gpc == 32 ? 0xFFFFFFFFull : ((1ull << gpc) - 1ull);
-                    const uint64_t bits = 1ull << grp;
                     uint64_t* w = reinterpret_cast<uint64_t*>(p.ws) + 2ull * c;
-                    const uint64_t prev = __hip_atomic_fetch_xor(w, (bits << 32) | V, __ATOMIC_RELAXED,
-                                                                 __HIP_MEMORY_SCOPE_AGENT);
-                    if (((prev >> 32) ^ bits) == full) {
-                        __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        raw = (uint32_t)prev ^ V;
+                    const uint64_t full = gpc == 32 ? 0xFFFFFFFFull : ((1ull << gpc) - 1ull);
+                    arrive_mask(w, 1ull << grp, V, full, [&](uint32_t r) {
+                        raw = r;
                         last_arrival = 1;
-                    }
-                } else {  // more than 32 workgroups per chunk: xor, then count arrivals
-                    uint32_t* accw = p.ws + 4ull * c;
-                    const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-                    const uint32_t tk = __hip_atomic_fetch_add(accw + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (tk + 1u == gpc) {
-                        raw = __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(accw + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    });
+                } else {  // more than 32 workgroups per chunk
+                    arrive_count(p.ws + 4ull * c, V, 1u, gpc, [&](uint32_t r) {
+                        raw = r;
                         last_arrival = 1;
-                    }
+                    });
                 }
-                if (last_arrival) {
-                    const uint32_t computed = ~(raw ^ p.c3);  // the lane constants carry c_inv
-                    const uint32_t code = computed == stored ? ZHIP_ST_OK : ZHIP_ST_CRC_MISMATCH;
-                    zhip_status st = {code, stored, computed, 0u};
-                    p.status[c] = st;
-                    if (code != ZHIP_ST_OK) atomicOr(p.errflag, 1u << code);
-                }
+                if (last_arrival) crc_verdict(p, c, stored, raw);  // the lane constants carry c_inv
             }
         }
     }
@@ -446,7 +434,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 // Production for transposed layouts with a CRC since round 4: C3 28.9 vs
 // 30.3-30.6 us graph-timed (profiles/r04/k/arms_c3.jsonl); ZHIP_TUNE_ARM 5
 // (or 1 / 2, its publication arms) takes k_decode_tile4.
-// (tileg_arrive: zhip_decode_common.h)
+// (tileg_arrive: zhip_arrival.h)
 
 template <int N>
 struct TileMapN {
@@ -586,39 +574,24 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
                     bool any_ne;
                     last_arrival = tileg_arrive<true>(p.ws, p.n_chunks, c, grp, gpc, 2u, V, false, raw, any_ne) ? 1u : 0u;
                 } else if (gpc <= 32) {
-                    const uint64_t full = gpc == 32 ? 0xFFFFFFFFull : ((1ull << gpc) - 1ull);
-                    const uint64_t bits = 1ull << grp;
                     uint64_t* w = reinterpret_cast<uint64_t*>(p.ws) + (uint64_t)(kPubLine / 2u) * c;
-                    const uint64_t prev = __hip_atomic_fetch_xor(w, (bits << 32) | V, __ATOMIC_RELAXED,
-                                                                 __HIP_MEMORY_SCOPE_AGENT);
-                    if (((prev >> 32) ^ bits) == full) {
-                        __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        raw = (uint32_t)prev ^ V;
+                    const uint64_t full = gpc == 32 ? 0xFFFFFFFFull : ((1ull << gpc) - 1ull);
+                    arrive_mask(w, 1ull << grp, V, full, [&](uint32_t r) {
+                        raw = r;
                         last_arrival = 1;
-                    }
+                    });
                 } else if (gpc <= 256u) {  // subwords of 16 workgroups (tile pairs of large chunks;
                     // two tiles: on lines of their own, as k_decode_tilegw's two-tile form)
                     bool any_ne;
                     last_arrival = tileg_arrive<NT == 2>(p.ws, p.n_chunks, c, grp, gpc, (gpc + 15u) / 16u, V, false, raw,
                                                 any_ne) ? 1u : 0u;
-                } else {  // more than 256 workgroups per chunk: xor, then count arrivals
-                    uint32_t* accw = p.ws + 4ull * c;
-                    const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-                    const uint32_t tk = __hip_atomic_fetch_add(accw + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (tk + 1u == gpc) {
-                        raw = __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(accw + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {  // more than 256 workgroups per chunk
+                    arrive_count(p.ws + 4ull * c, V, 1u, gpc, [&](uint32_t r) {
+                        raw = r;
                         last_arrival = 1;
-                    }
+                    });
                 }
-                if (last_arrival) {
-                    const uint32_t computed = ~(raw ^ p.c3);  // the lane constants carry c_inv
-                    const uint32_t code = computed == stored ? ZHIP_ST_OK : ZHIP_ST_CRC_MISMATCH;
-                    zhip_status st = {code, stored, computed, 0u};
-                    p.status[c] = st;
-                    if (code != ZHIP_ST_OK) atomicOr(p.errflag, 1u << code);
-                }
+                if (last_arrival) crc_verdict(p, c, stored, raw);  // the lane constants carry c_inv
             }
         }
     }
@@ -765,7 +738,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             if (gpc <= 16u || p.n_sub) {
                 bool any_ne;
                 last_one = tileg_arrive(p.ws, p.n_chunks, c, grp, gpc, p.n_sub, V, false, raw, any_ne);
-            } else {  // more than 256 groups per chunk: XOR, then count arrivals
+            } else {  // more than 256 groups per chunk: XOR, then count arrivals (arrive_count and
+                // crc_verdict of zhip_arrival.h, written out: through them this kernel's generated
+                // code changes outside the arrival block)
                 uint32_t* accw = p.ws + 4ull * c;
                 const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
@@ -968,7 +943,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             } else if (gpc <= 16u || nsub) {
                 bool any_ne;
                 last_one = tileg_arrive<SPR>(p.ws, p.n_chunks, c, wg, gpc, nsub, V, false, raw, any_ne);
-            } else {  // more than 256 groups per chunk: XOR, then count arrivals
+            } else {  // more than 256 groups per chunk: XOR, then count arrivals (arrive_count and
+                // crc_verdict of zhip_arrival.h, written out: through them this kernel's generated
+                // code changes outside the arrival block)
                 uint32_t* accw = p.ws + 4ull * c;
                 const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
@@ -1146,11 +1123,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     uint32_t crc = 0;
     if constexpr (CRC) {
         crc = ~((uint32_t)all ^ p.c3);  // kq4 carries t_c_inv
-        uint8_t* tr = cp + p.g.nbytes;  // LE trailer (crc32c_.py:64-68)
-        tr[0] = (uint8_t)crc;
-        tr[1] = (uint8_t)(crc >> 8);
-        tr[2] = (uint8_t)(crc >> 16);
-        tr[3] = (uint8_t)(crc >> 24);
+        put_le_u32(cp + p.g.nbytes, crc);
     }
     zhip_status st = {ZHIP_ST_OK, crc, crc, 0u};
     p.status[c] = st;
@@ -1366,7 +1339,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     }
     __syncthreads();
     if (t != 0) return;
-    // arrival word: workgroups arrived (low 16 bits) | non-empty ones (high 16)
+    // arrival word: workgroups arrived (low 16 bits) | non-empty ones (high 16): the counted form
+    // of zhip_arrival.h with the non-empty count in the ticket, written out (a helper moved the
+    // non-empty store and with it code outside the arrival block)
     const bool ne = (s_ne[0] | s_ne[1] | s_ne[2] | s_ne[3]) != 0u;
     uint32_t* accw = p.ws + 4ull * c;
     if constexpr (CRC) {
@@ -1382,11 +1357,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     if constexpr (CRC) {
         const uint32_t raw = __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t crc = ~(gf_mul(raw, p.c_inv) ^ p.c3);
-        uint8_t* tr = cp + p.g.nbytes;  // LE trailer (crc32c_.py:64-68)
-        tr[0] = (uint8_t)crc;
-        tr[1] = (uint8_t)(crc >> 8);
-        tr[2] = (uint8_t)(crc >> 16);
-        tr[3] = (uint8_t)(crc >> 24);
+        put_le_u32(cp + p.g.nbytes, crc);
         zhip_status st = {ZHIP_ST_OK, crc, crc, 0u};
         p.status[c] = st;
     } else {
@@ -1562,7 +1533,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             return;
         }
         p.nonempty[c] = any_ne ? 1u : 0u;
-    } else {  // more than 256 groups per chunk: arrival count | non-empty count word
+    } else {  // more than 256 groups per chunk: arrival count | non-empty count word (as k_encode_tile)
         uint32_t* accw = p.ws + 4ull * c;
         if constexpr (CRC) {
             const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1577,11 +1548,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     }
     if constexpr (CRC) {
         const uint32_t crc = ~(raw ^ p.c3);  // ku carries t_c_inv
-        uint8_t* tr = chunk + p.g.nbytes;    // LE trailer (crc32c_.py:64-68)
-        tr[0] = (uint8_t)crc;
-        tr[1] = (uint8_t)(crc >> 8);
-        tr[2] = (uint8_t)(crc >> 16);
-        tr[3] = (uint8_t)(crc >> 24);
+        put_le_u32(chunk + p.g.nbytes, crc);
         zhip_status st = {ZHIP_ST_OK, crc, crc, 0u};
         p.status[c] = st;
     } else {

@@ -29,6 +29,7 @@
 #include "zhip_dispatch.h"
 #include "zhip_fill_eq.h"
 #include "zhip_decode_common.h"
+#include "zhip_arrival.h"
 
 namespace zhip {
 
@@ -100,13 +101,6 @@ __device__ __forceinline__ void store_block(uint8_t* cp, int32_t o, uint4 v, uin
     for (uint32_t i = 0; i < n; ++i) cp[o + i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3u)));
 }
 
-__device__ __forceinline__ void put_le_u32(uint8_t* d, uint32_t v) {  // any alignment
-    d[0] = (uint8_t)v;
-    d[1] = (uint8_t)(v >> 8);
-    d[2] = (uint8_t)(v >> 16);
-    d[3] = (uint8_t)(v >> 24);
-}
-
 template <bool CRC, bool FAST, int ITEM, int SWAP>
 __global__ __launch_bounds__(kThreads) void k_encode(const EncodeParams p) {
     constexpr int K = kDefaultBlocks;
@@ -172,6 +166,8 @@ __global__ __launch_bounds__(kThreads) void k_encode(const EncodeParams p) {
                 if (t == 0) {
                     uint32_t V = s_red[parity][0] ^ s_red[parity][1] ^ s_red[parity][2] ^ s_red[parity][3];
                     V = gf_mul(V, p.kunit[sidx]);
+                    // arrive_count (zhip_arrival.h) written out: run_len is formed between the
+                    // wait and the ticket, and moving it changes this kernel's body
                     uint32_t* accw = p.ws + 4ull * c;
                     const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
@@ -182,11 +178,7 @@ __global__ __launch_bounds__(kThreads) void k_encode(const EncodeParams p) {
                         const uint32_t raw = __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         __hip_atomic_store(accw + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         const uint32_t crc = ~(gf_mul(raw, p.c_inv) ^ p.c3);
-                        uint8_t* tr = cp + p.g.nbytes;  // LE trailer (crc32c_.py:64-68)
-                        tr[0] = (uint8_t)crc;
-                        tr[1] = (uint8_t)(crc >> 8);
-                        tr[2] = (uint8_t)(crc >> 16);
-                        tr[3] = (uint8_t)(crc >> 24);
+                        put_le_u32(cp + p.g.nbytes, crc);  // LE trailer (crc32c_.py:64-68)
                         zhip_status st = {ZHIP_ST_OK, crc, crc, 0u};
                         p.status[c] = st;
                     }
@@ -286,26 +278,16 @@ __device__ __forceinline__ void enc_run_end(const EncodeParams& p, const zhip_ch
         if (t != 0) return;
         const uint32_t V = red[0] ^ red[1] ^ red[2] ^ red[3];
         uint32_t raw = 0, last = 0;
+        auto done = [&](uint32_t r) {
+            raw = r;
+            last = 1;
+        };
         if (p.nseg <= 32) {
-            const uint64_t full = p.nseg >= 32 ? 0xFFFFFFFFull : ((1ull << p.nseg) - 1ull);
+            const uint64_t full = mask_of(p.nseg);
             uint64_t* w = reinterpret_cast<uint64_t*>(p.ws) + (uint64_t)p.pub_stride * c;
-            const uint64_t prev =
-                __hip_atomic_fetch_xor(w, ((uint64_t)bits << 32) | V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (((prev >> 32) ^ bits) == full) {
-                __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                raw = (uint32_t)prev ^ V;
-                last = 1;
-            }
+            arrive_mask(w, bits, V, full, done);
         } else {
-            uint32_t* accw = p.ws + 4ull * c;
-            const uint32_t prev = __hip_atomic_fetch_xor(accw, V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-            const uint32_t tk = __hip_atomic_fetch_add(accw + 2, n_run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk + n_run == p.nseg) {
-                raw = __hip_atomic_exchange(accw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(accw + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                last = 1;
-            }
+            arrive_count(p.ws + 4ull * c, V, n_run, p.nseg, done);
         }
         if (last) {
             const uint32_t crc = ~(raw ^ p.c3);  // kpair carries c_inv

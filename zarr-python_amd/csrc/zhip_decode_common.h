@@ -1,7 +1,7 @@
 // Decode building blocks shared by k_decode (decode.hip) and k_decode_rows
 // (decode_rows.hip): unit resolution through the shard index, unit loads,
-// CRC finalisation, fused shard-index verification and the deferred arrival
-// retire.  See decode.hip for the work decomposition and the CRC algebra.
+// fused shard-index verification.  The arrival and verdict protocol is
+// zhip_arrival.h.  See decode.hip for the work decomposition and the CRC algebra.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -201,21 +201,6 @@ __device__ __forceinline__ void load_unit(const DecodeParams& p, const Unit& U, 
     }
 }
 
-// Last unit of chunk c has arrived: turn the accumulator into the CRC-32C value
-// and compare with the stored little-endian trailer (crc32c_.py:41-49).
-__device__ __forceinline__ void finalize_chunk(const DecodeParams& p, uint32_t c, uint32_t stored,
-                                               uint32_t raw) {
-    const uint32_t computed = ~(gf_mul(raw, p.c_inv) ^ p.c3);
-    const uint32_t code = computed == stored ? ZHIP_ST_OK : ZHIP_ST_CRC_MISMATCH;
-    zhip_status st;
-    st.code = code;
-    st.stored = stored;
-    st.computed = computed;
-    st.aux = 0;
-    p.status[c] = st;
-    if (code != ZHIP_ST_OK) atomicOr(p.errflag, 1u << code);
-}
-
 // The LE u32 CRC trailer at cp + n through the scalar cache: the aligned dword
 // pair covering it (the arena keeps readable slack past every blob), shifted.
 __device__ __forceinline__ uint32_t load_trailer_uniform(const uint8_t* cp, uint32_t n) {
@@ -264,41 +249,6 @@ __device__ __forceinline__ uint32_t load_trailer(const uint8_t* cp, uint32_t n) 
     return (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
 }
 
-// ---- deferred CRC verdicts (zarrhip.h), shared by the decode kernels that
-// publish without a returning atomic ----
-// {word, stored} of chunk c in the OTHER bank (the previous launch's verdict),
-// read by the chunk's first workgroup; one address for every lane (`zero`
-// otherwise), so every path issues the same vector load.
-__device__ __forceinline__ uint64_t dv_prev(const DecodeParams& p, uint32_t c, bool first, const void* zero) {
-    return __hip_atomic_load(reinterpret_cast<const uint64_t*>(
-                                 first ? p.ws + 4ull * c + 2u * (p.dv_bank ^ 1u) : static_cast<const uint32_t*>(zero)),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One lane: xor the workgroup's (chunk-referenced) contribution into this
-// launch's bank word -- the first workgroup also folds in c3 ^ ~stored, so
-// the word ends as computed ^ stored -- and record the trailer.  The atomic's
-// result is unused: nobody waits for its round trip.
-__device__ __forceinline__ void dv_publish(const DecodeParams& p, uint32_t c, bool first, uint32_t V,
-                                           uint32_t stored) {
-    uint32_t* w = p.ws + 4ull * c + 2u * p.dv_bank;
-    __hip_atomic_fetch_xor(w, V ^ (first ? (p.c3 ^ ~stored) : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (first) __hip_atomic_store(w + 1, stored, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One lane of the first workgroup, after the chunk's own status: a nonzero
-// previous verdict is the previous launch's mismatch (sticky status + error
-// bit); its word is cleared for the launch after this one.
-__device__ __forceinline__ void dv_settle(const DecodeParams& p, uint32_t c, uint64_t prev) {
-    const uint32_t pw = (uint32_t)prev, ps = (uint32_t)(prev >> 32);
-    if (pw != 0u) {
-        zhip_status st = {ZHIP_ST_CRC_MISMATCH, ps, pw ^ ps, 0u};
-        p.status[c] = st;
-        atomicOr(p.errflag, 1u << ZHIP_ST_CRC_MISMATCH);
-        __hip_atomic_store(p.ws + 4ull * c + 2u * (p.dv_bank ^ 1u), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 // CRC-32C check of one shard index (payload idx_nbytes + LE trailer) by one
 // workgroup: the same per-thread Horner chain as a data unit ending at idx_E
 // (reference point idx_E + 4096), reduced over the workgroup.  `red` is a
@@ -320,6 +270,21 @@ __device__ __forceinline__ uint4 index_prefetch(const DecodeParams& p, uint32_t 
     uint4 v;
     __builtin_memcpy(&v, a, 16);
     return v;
+}
+
+// One lane: shard index j's status from the workgroup's four reduced words
+// (`ok`: the blob has the index's length) and its error bit.
+__device__ __forceinline__ void index_verdict(const DecodeParams& p, uint32_t j, bool ok, const uint8_t* cp,
+                                              const uint32_t* red) {
+    zhip_status st = {ZHIP_ST_LENGTH_MISMATCH, 0u, 0u, 0u};
+    if (ok) {
+        const uint32_t V = red[0] ^ red[1] ^ red[2] ^ red[3];
+        st.stored = load_trailer(cp, p.idx_nbytes);
+        st.computed = ~(gf_mul(V, p.idx_c_inv) ^ p.idx_c3);
+        st.code = st.computed == st.stored ? ZHIP_ST_OK : ZHIP_ST_CRC_MISMATCH;
+    }
+    p.idx_status[j] = st;
+    if (st.code != ZHIP_ST_OK) atomicOr(p.errflag, 1u << st.code);
 }
 
 __device__ __forceinline__ void verify_index(const DecodeParams& p, uint32_t j, int t, uint32_t kth,
@@ -347,32 +312,7 @@ __device__ __forceinline__ void verify_index(const DecodeParams& p, uint32_t j, 
     __syncthreads();  // red may still be read from a previous index
     if ((t & 63) == 0) red[t >> 6] = v;
     __syncthreads();
-    if (t == 0) {
-        zhip_status st = {ZHIP_ST_LENGTH_MISMATCH, 0u, 0u, 0u};
-        if (ok) {
-            const uint32_t V = red[0] ^ red[1] ^ red[2] ^ red[3];
-            st.stored = load_trailer(cp, p.idx_nbytes);
-            st.computed = ~(gf_mul(V, p.idx_c_inv) ^ p.idx_c3);
-            st.code = st.computed == st.stored ? ZHIP_ST_OK : ZHIP_ST_CRC_MISMATCH;
-        }
-        p.idx_status[j] = st;
-        if (st.code != ZHIP_ST_OK) atomicOr(p.errflag, 1u << st.code);
-    }
-}
-
-struct Pending {  // thread 0's outstanding arrival for one run, checked one run later
-    uint64_t prev;
-    uint32_t stored, c, bits, V, valid;
-};
-
-__device__ __forceinline__ void retire(const DecodeParams& p, Pending& q, uint64_t full) {
-    if (!q.valid) return;
-    q.valid = 0;
-    if (((q.prev >> 32) ^ q.bits) == full) {
-        uint64_t* w = reinterpret_cast<uint64_t*>(p.ws) + 2ull * q.c;
-        __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        finalize_chunk(p, q.c, q.stored, (uint32_t)q.prev ^ q.V);
-    }
+    if (t == 0) index_verdict(p, j, ok, cp, red);
 }
 
 // ---- the pair kernel's CRC step (k_decode_pair / k_decode_il / k_decode_tile4f;
@@ -475,95 +415,6 @@ __device__ __forceinline__ uint32_t lanemul_reg(uint32_t k, uint32_t a) {
     for (int j = 1; j < 10; ++j) q = (q >> 3) ^ r3(q & 7u) ^ sel3((a >> (3 * j)) & 7u);
     const uint32_t w = a >> 30;
     return (q >> 2) ^ r2(q & 3u) ^ (k & (0u - ((w >> 1) & 1u))) ^ (k1 & (0u - (w & 1u)));
-}
-
-// Arrival of one workgroup of a grouped tile kernel (k_decode_tileg /
-// k_encode_tileg) with its CRC contribution v and non-empty bit: 64-bit words
-// CRC (low 32) | arrival bits (32..47) | non-empty bits (48..63), one relaxed
-// XOR per level.  Up to 16 groups per chunk the chunk word is the only level;
-// up to 256 the groups first meet in words of 16 (the workspace tail after the
-// 4 words per chunk), whose completing arrival carries the subgroup's XOR on
-// to the chunk word.  True for the arrival completing the chunk, with the
-// XOR of every contribution and whether any group was non-empty.
-// SPR: every subword and the chunk's word on a 128-byte line of its own
-// (chunk lines at ws + 32 c, subword lines after all chunk lines;
-// zhip_plan_info sizes the workspace for it), so a chunk's arrivals do not
-// meet on one line: production for k_decode_tilegw's two-tile form -- C3 in
-// 128^3 chunks, 256 arrivals per chunk, 28.94 / 29.00 vs 29.57 / 29.28 us
-// graph-timed (profiles/r05/aa/; tuning arm 48 keeps the packed words); in
-// k_encode_tileg (128 arrivals per chunk) neutral, tuning arm 47.
-template <bool SPR = false>
-__device__ __forceinline__ bool tileg_arrive(uint32_t* ws, uint32_t n_chunks, uint32_t c, uint32_t grp,
-                                             uint32_t gpc, uint32_t n_sub, uint32_t v, bool ne, uint32_t& raw,
-                                             bool& any_ne) {
-    if (n_sub) {
-        const uint32_t sg = grp >> 4;
-        const uint32_t in_sg = min(16u, gpc - (sg << 4));
-        uint64_t* sw = SPR ? reinterpret_cast<uint64_t*>(ws + 32ull * n_chunks) + ((uint64_t)c * n_sub + sg) * 16u
-                           : reinterpret_cast<uint64_t*>(ws + 4ull * n_chunks) + (uint64_t)c * n_sub + sg;
-        const uint64_t b = 1ull << (grp & 15u);
-        const uint64_t prev = __hip_atomic_fetch_xor(sw, (b << 32) | (ne ? b << 48 : 0ull) | v, __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_AGENT);
-        if ((((prev >> 32) & 0xFFFFull) ^ b) != (1ull << in_sg) - 1ull) return false;
-        __hip_atomic_store(sw, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v ^= (uint32_t)prev;
-        ne = ne || ((prev >> 48) & 0xFFFFull) != 0ull;
-        grp = sg;
-        gpc = n_sub;
-    }
-    uint64_t* cw = reinterpret_cast<uint64_t*>(ws) + (SPR ? 16ull : 2ull) * c;
-    const uint64_t b = 1ull << grp;
-    const uint64_t prev = __hip_atomic_fetch_xor(cw, (b << 32) | (ne ? b << 48 : 0ull) | v, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-    if ((((prev >> 32) & 0xFFFFull) ^ b) != (1ull << gpc) - 1ull) return false;
-    __hip_atomic_store(cw, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    raw = (uint32_t)prev ^ v;
-    any_ne = ne || ((prev >> 48) & 0xFFFFull) != 0ull;
-    return true;
-}
-
-// tileg_arrive with the look-back finalizer (round 6; tuning arms 62 / 63):
-// the subwords of 16 arrivals on lines of their own (tileg_arrive SPR's
-// layout; one word of up to 16 when n_sub is 0).  Every workgroup but the
-// chunk's last (grp = gpc - 1) xors its bit | non-empty bit | v with a
-// NON-returning atomic and returns false; the last one polls every subword
-// (one lane, relaxed agent loads) until all the other arrivals are in, resets
-// them and returns true with the chunk's raw sum and non-empty flag.  The
-// caller takes it only while fewer chunks than CUs are in the launch (the
-// finalizers then never hold every slot; publish_lb, decode_rows.hip).
-__device__ __forceinline__ bool tileg_arrive_lb(uint32_t* ws, uint32_t n_chunks, uint32_t c, uint32_t grp,
-                                                uint32_t gpc, uint32_t n_sub, uint32_t v, bool ne, uint32_t& raw,
-                                                bool& any_ne) {
-    const uint32_t nsw = n_sub ? n_sub : 1u;
-    uint64_t* const base = n_sub ? reinterpret_cast<uint64_t*>(ws + 32ull * n_chunks) + (uint64_t)c * n_sub * 16u
-                                 : reinterpret_cast<uint64_t*>(ws) + 16ull * c;
-    const uint32_t sg = n_sub ? grp >> 4 : 0u;
-    const uint64_t b = 1ull << (n_sub ? (grp & 15u) : grp);
-    if (grp + 1u < gpc) {
-        (void)__hip_atomic_fetch_xor(base + 16ull * sg, (b << 32) | (ne ? b << 48 : 0ull) | v, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-        return false;
-    }
-    uint32_t acc = v;
-    bool nn = ne;
-    for (uint32_t s = 0; s < nsw; ++s) {
-        const uint32_t in_s = n_sub ? min(16u, gpc - 16u * s) : gpc;
-        uint64_t expect = (1ull << in_s) - 1ull;
-        if (s == sg) expect ^= b;
-        uint64_t* const w = base + 16ull * s;
-        uint64_t cur;
-        for (;;) {
-            cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (((cur >> 32) & 0xFFFFull) == expect) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        acc ^= (uint32_t)cur;
-        nn = nn || ((cur >> 48) & 0xFFFFull) != 0ull;
-    }
-    raw = acc;
-    any_ne = nn;
-    return true;
 }
 
 }  // namespace zhip
