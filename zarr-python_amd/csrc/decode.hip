@@ -639,12 +639,41 @@ static bool launch_row_arm(const Launch& L, bool il, int& rc) {
 }
 #endif
 
+#if ZHIP_TUNING
+// Arms 64 / 65 store through a buffer resource of 0x7FFFFFF0 records based at
+// the chunk's out position, at the 32-bit offset rel + lane_off: a 16-byte
+// store that starts before record 0 or ends past the last is dropped by the
+// hardware.  zhip_rows_map admits rel up to INT32_MAX and lane_off adds up to
+// a step of rows, so the arm is taken only while every store of the plan's
+// affine form fits the resource; otherwise the launch keeps the production
+// instantiation.  A chunk whose selection record is not whole (a C caller's
+// partial selection under ZHIP_DF_WHOLE) takes its rel from the row map
+// instead: for a lane that writes, rel + lane_off is then the whole chunk's
+// offset of the same element less the selection's start, so with
+// non-negative out strides it lies between 0 and the bound checked here;
+// with a negative stride nothing bounds it and the arm is declined.
+static bool il_buffer_stores_fit(const DecodeParams& p) {
+    const int64_t rps = (int64_t)kWgStride >> p.row_shift;
+    const int64_t lane_hi = (rps - 1) * p.r_oy + ((int64_t)1 << p.row_shift) - 16;  // the last lane's lane_off
+    const int64_t lane_lo = std::min<int64_t>((rps - 1) * p.r_oy, 0);
+    const uint32_t n_st = p.nseg * (uint32_t)kDefaultBlocks;
+    if (p.r_oy < 0 || p.aff_B < 0 || p.aff_C < 0) return false;
+    for (uint32_t st = 0; st < n_st; ++st) {
+        const int64_t rel = (int64_t)(st >> p.aff_sh) * p.aff_B + (int64_t)(st & p.aff_mask) * p.aff_C + p.aff_D;
+        if (rel + lane_lo < 0 || rel + std::max(lane_hi, lane_lo) + 16 > 0x7FFFFFF0ll) return false;
+    }
+    return true;
+}
+#endif
+
 // k_decode_il's instantiation: production, or in the tuning build the arm's
 // (nullptr where the arm has none for this item type)
 static KernelFn pick_il_kernel(const Launch& L) {
 #if ZHIP_TUNING
     const DecodeParams& p = L.p;
     const uint32_t tune = L.tune;
+    if ((g_tune_arm == kArmIlStoreWt || g_tune_arm == kArmIlStoreNt) && p.aff_ok && !il_buffer_stores_fit(p))
+        return select_il_kernel(L.crc, L.item, L.swap, true);
     // (arms 1 / 2 are k_decode_il's own; every other arm keeps production here)
     // (58: the look-back finalizer, while fewer chunks than CUs)
     if (g_tune_arm == kArmPub16 || g_tune_arm == kArmDeferred ||
