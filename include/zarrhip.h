@@ -993,6 +993,12 @@ uint32_t zhip_emulate_chunk_crc_il(const zhip_plan *plan, const uint8_t *data);
  * A_1024 tables, per-(span, lane) constants); 0xFFFFFFFF when the plan has no
  * xw layout.  Test hook. */
 uint32_t zhip_emulate_chunk_crc_xw(const zhip_plan *plan, const uint8_t *data);
+/* The same for k_decode_il's full-row form (lane l of span group r: one
+ * A_1024 chain through the 8 P blocks of P consecutive 8 KiB spans, the xw
+ * lane constant of the group's last span); 0xFFFFFFFF when the plan has no xw
+ * layout or its span count is no multiple of P.  The decode takes P = 4.
+ * Test hook. */
+uint32_t zhip_emulate_chunk_crc_ilx(const zhip_plan *plan, const uint8_t *data, uint32_t P);
 /* The table image zhip_plan_upload would put on the device, built on the host
  * (the emulations above read the same): which = 0 the row tables, 1 the tile
  * tables.  Copies up to cap u32 words to out (may be null); returns the

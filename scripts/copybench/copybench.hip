@@ -364,8 +364,63 @@ __global__ __launch_bounds__(256) void k_scatter_g(const uint8_t* __restrict__ s
     }
 }
 
-// mode: 0 natural (K 1, 2, 4, 8, 16), 1 interleaved (S 4 / 8, K 8), 2 x-quads
-// (K 4, 8, 16), 3 x-quads by wave (K 8); ce 32 = C4, 64 = the headline
+// x-quads by wave in P passes: wave v on chunk 4 (w / per) + v streams P
+// consecutive 8 KiB spans of it, 8 blocks per lane and pass at a 1 KiB lane
+// stride (MODE 3's order with P spans per workgroup).  PRE: the next pass's
+// loads go out before the current pass's stores (two register buffers),
+// otherwise after them.
+template <int P, bool PRE>
+__global__ __launch_bounds__(256) void k_scatter_xwp(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                     const ScatterGeo g) {
+    const uint32_t t = threadIdx.x, w = blockIdx.x;
+    const uint32_t per = g.spc / 2 / P;  // workgroups per group of four chunks
+    const uint32_t c = (w / per) * 4 + (t >> 6);
+    const uint32_t b0 = (w % per) * P * 8192 + 16 * (t & 63);
+    const uint8_t* cp = src + (uint64_t)c * g.cstride;
+    const uint32_t row = 4 * g.ce, plane = row * g.ce, c3 = g.cps * g.cps * g.cps;
+    const uint64_t N = (uint64_t)g.ce * g.cps * g.sps;
+    const uint32_t s = c / c3, i = c % c3;
+    const uint32_t sz = s / (g.sps * g.sps), sy = (s / g.sps) % g.sps, sx = s % g.sps;
+    const uint32_t iz = i / (g.cps * g.cps), iy = (i / g.cps) % g.cps, ix = i % g.cps;
+    uint4 v[PRE ? 2 : 1][8];
+    auto load = [&](int p, uint4* r) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const v4u_a1 x = *reinterpret_cast<const v4u_a1*>(cp + b0 + 8192 * p + 1024 * k);
+            r[k] = make_uint4(x.x, x.y, x.z, x.w);
+        }
+    };
+    auto store = [&](int p, const uint4* r) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t b = b0 + 8192 * p + 1024 * k;
+            const uint32_t z = b / plane, y = (b / row) % g.ce, xb = b % row;
+            const uint64_t o = (((sz * g.cps + iz) * g.ce + z) * N + (sy * g.cps + iy) * g.ce + y) * N * 4 +
+                               (uint64_t)(sx * g.cps + ix) * g.ce * 4 + xb;
+            v4u x = {r[k].x, r[k].y, r[k].z, r[k].w};
+            __builtin_nontemporal_store(x, reinterpret_cast<v4u*>(dst + o));
+        }
+    };
+    if constexpr (PRE) {
+        load(0, v[0]);
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            if (p + 1 < P) load(p + 1, v[(p + 1) & 1]);
+            store(p, v[p & 1]);
+        }
+    } else {
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            load(p, v[0]);
+            store(p, v[0]);
+        }
+    }
+}
+
+// mode: 0 natural (K 1, 2, 4, 8, 16), 1 interleaved (S 4 / 8 / 32, K 8), 2
+// x-quads (K 4, 8, 16), 3 x-quads by wave (K 8), 4 / 5 x-quads by wave in S =
+// 2 or 4 passes of K 8 (4: loads after the stores, 5: before them); ce 32 =
+// C4, 64 = the headline
 extern "C" int cb_scatter_geo(const void* src, void* dst, uint64_t cstride, int ce, int mode, int K, int S,
                               void* stream) {
     ScatterGeo g;
@@ -388,9 +443,17 @@ extern "C" int cb_scatter_geo(const void* src, void* dst, uint64_t cstride, int 
     if (mode == 2 && K == 4) fn = k_scatter_g<2, 4, 1>;
     if (mode == 2 && K == 8) fn = k_scatter_g<2, 8, 1>;
     if (mode == 2 && K == 16) fn = k_scatter_g<2, 16, 1>;
+    if (mode == 1 && K == 8 && S == 32) fn = k_scatter_g<1, 8, 32>;
     if (mode == 3 && K == 8) fn = k_scatter_g<3, 8, 1>;
+    if (mode == 4 && K == 8 && S == 2) fn = k_scatter_xwp<2, false>;
+    if (mode == 4 && K == 8 && S == 4) fn = k_scatter_xwp<4, false>;
+    if (mode == 5 && K == 8 && S == 2) fn = k_scatter_xwp<2, true>;
+    if (mode == 5 && K == 8 && S == 4) fn = k_scatter_xwp<4, true>;
     if (!fn) return -1;
-    const uint32_t grid = mode == 3 ? n_chunks / 4 * (g.spc / 2) : n_steps / K;
+    if (mode == 1 && n_steps % (K * S)) return -3;
+    if (mode >= 4 && (g.spc / 2) % S) return -3;
+    const uint32_t grid = mode == 3 ? n_chunks / 4 * (g.spc / 2)
+                        : mode >= 4 ? n_chunks / 4 * (g.spc / 2 / S) : n_steps / K;
     hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (uint8_t*)dst, g);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -117,7 +117,11 @@ def main():
     srcg = [torch.empty(n_inner * cstride + 64, dtype=torch.uint8, device=dev).fill_(5) for _ in range(Rg)]
     for nm, mode, K, S in (("nat_K1", 0, 1, 1), ("nat_K2", 0, 2, 1), ("nat_K4", 0, 4, 1), ("nat_K8", 0, 8, 1),
                            ("nat_K16", 0, 16, 1), ("il_S4_K8", 1, 8, 4), ("il_S8_K8", 1, 8, 8),
-                           ("xq_K4", 2, 4, 1), ("xq_K8", 2, 8, 1), ("xq_K16", 2, 16, 1), ("xw_K8", 3, 8, 1)):
+                           ("il_S32_K8", 1, 8, 32),
+                           ("xq_K4", 2, 4, 1), ("xq_K8", 2, 8, 1), ("xq_K16", 2, 16, 1), ("xw_K8", 3, 8, 1),
+                           # xw in P passes per workgroup (S carries P): loads after / before the stores
+                           ("xw_P2_K8", 4, 8, 2), ("xw_P4_K8", 4, 8, 4),
+                           ("xw_P2_K8_pre", 5, 8, 2), ("xw_P4_K8_pre", 5, 8, 4)):
         arms[f"scatterg_{nm}"] = graph_of(lambda i, sh, mode=mode, K=K, S=S: cb.cb_scatter_geo(
             srcg[i % Rg].data_ptr(), dsts[i % Rg].data_ptr(), cstride, ce, mode, K, S, ctypes.c_void_p(sh)))
     if os.environ.get("COPIES", "1") == "0":

@@ -1413,6 +1413,24 @@ uint32_t zhip_emulate_chunk_crc_xw(const zhip_plan* plan, const uint8_t* data) {
                          [](uint32_t a, uint32_t k) { return gf_mul(a, k); });
 }
 
+// k_decode_il's full-row form: lane l of span group r runs one A_1024 chain
+// through the blocks at 8192 (P r + s) + 1024 k + 16 l (s < P, k < 8) and
+// ends on the group's last span, so its constant is k_decode_xw's of span
+// P r + P - 1 (the xw lane table serves every P).  0xFFFFFFFF when the plan
+// has no xw layout or its span count is no multiple of P.  Test hook.
+uint32_t zhip_emulate_chunk_crc_ilx(const zhip_plan* plan, const uint8_t* data, uint32_t P) {
+    if (!plan || !plan->xw_P || P == 0 || plan->xw_P % P) return 0xFFFFFFFFu;
+    const int64_t lo_frame = (int64_t)plan->E - (int64_t)plan->nseg * kDefaultBlocks * kWgStride;
+    const std::vector<uint32_t> h = build_row_tables(*plan);
+    const TabSet& S = plan->tl.xw;
+    const uint64_t n_lanes = (uint64_t)(plan->xw_P / P) * 64;
+    std::vector<uint32_t> kl(n_lanes);
+    for (uint64_t i = 0; i < n_lanes; ++i) kl[i] = h[S.klane.off + ((i / 64) * P + (P - 1)) * 64 + i % 64];
+    return emulate_lanes(plan, data, &h[S.tab.off], kl.data(), n_lanes, kDefaultBlocks * P,
+                         [&](int64_t i, int64_t k) { return lo_frame + 8192 * (i / 64) * (int64_t)P + 1024 * k + 16 * (i % 64); },
+                         [](uint32_t a, uint32_t k) { return gf_mul(a, k); });
+}
+
 // CPU self-test of the identities the kernels rely on.  Returns 0 when all hold.
 int zhip_selftest(void) {
     // 1. top byte of T[i] is a bijection (needed for the inverse byte step)

@@ -754,9 +754,32 @@ static bool takes_ilw512(const Launch& L, bool il) {
            (L.tune & ~kTuneStamp) == 0;
 }
 
+// Fused launches (launch_decode_multi) whose every member is a k_decode_il
+// launch of more than kIlwMaxUnits units and whole groups of four chunks, on
+// plans with the xw tables, take the full-row form (wave
+// w of a workgroup on chunk 4 G + w, decode_rows.hip ilx_body), at most 32
+// workgroups per group (the mask form of the publication).  Chunks of a
+// group need not be neighbours in the out or whole reads: each wave stores
+// through its own chunk's row map (or the affine form, checked per chunk).
+// (Tuning build: any arm or tuning bit, kTuneNoXw for the A/B, keeps the
+// interleaved form.)
+static bool takes_fullrow(const Launch& L, bool il) {
+    const DecodeParams& p = L.p;
+    return il && L.crc && p.xw != 0 && p.xw % kIlxSpans == 0u && p.xw / kIlxSpans <= 32u &&
+           p.n_units > kIlwMaxUnits && p.n_chunks % 4u == 0u && g_tune_arm == kArmProduction && L.tune == 0u;
+}
+
+// its grid: one workgroup per kIlxSpans spans of a group of four chunks, or
+// the fused index checks if there are more of them
+static uint64_t fullrow_grid(const DecodeParams& p) {
+    const uint64_t g = (uint64_t)(p.n_chunks / 4u) * (p.xw / kIlxSpans);
+    return g > p.n_idx ? g : p.n_idx;
+}
+
 // Whole-row layouts with a row map, 32 KiB units: one workgroup per unit,
 // half unit or pair of units, non-persistent.  The production rule reads top
-// to bottom: lead4 / lead8, lead, ilh, ilw512, il, duo, pair.
+// to bottom: lead4 / lead8, lead, ilh, ilw512, il (full-row, else
+// interleaved), duo, pair.
 static int launch_row_units(const Launch& L) {
     const DecodeParams& p = L.p;
     const uint32_t tune = L.tune;
@@ -779,6 +802,8 @@ static int launch_row_units(const Launch& L) {
         return fire(select_ilw_kernel(L.item, L.swap, form, false, p.aff_ok != 0), "k_decode_ilw512",
                     unit_grid(p, p.n_units), 512, p, L.stream);
     }
+    // (the full-row form, takes_fullrow, is taken by fused launches only: alone, the headline's 512 workgroups
+    // are half a residency round and graph-time 27.7 us against 25.9 interleaved, profiles/r10/)
     if (il) return fire(pick_il_kernel(L), "k_decode_il", unit_grid(p, p.n_units), kThreads, p, L.stream);
     // one workgroup per pair of units (k_decode_pair)
     const int nu = (tune & kTuneSingle) ? 1 : 2;
@@ -913,13 +938,21 @@ int launch_decode_multi(const DecodeParams* ps, const int* max_grid, uint32_t n,
     MultiParams m{};
     MultiFn fn = nullptr;
     uint64_t total = 0;
+    // the full-row form when every launch alone would take it; a mixed grid
+    // keeps the interleaved form, which serves them all
+    bool fr = true;
     for (uint32_t i = 0; i < n; ++i) {
         const Launch L = make_launch(ps[i], stream, max_grid[i]);
         if (!takes_plain_il(L)) return ZHIP_E_UNSUPPORTED;
-        MultiFn f = select_il_multi_kernel(L.crc, L.item, L.swap, ps[i].aff_ok != 0);
+        fr = fr && takes_fullrow(L, true);
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const Launch L = make_launch(ps[i], stream, max_grid[i]);
+        MultiFn f = fr ? select_ilx_multi_kernel(L.crc, L.item, L.swap, ps[i].aff_ok != 0)
+                       : select_il_multi_kernel(L.crc, L.item, L.swap, ps[i].aff_ok != 0);
         if (!f || (i && f != fn)) return ZHIP_E_UNSUPPORTED;  // one instantiation for the whole grid
         fn = f;
-        const uint32_t grid = unit_grid(ps[i], ps[i].n_units);
+        const uint32_t grid = fr ? (uint32_t)fullrow_grid(ps[i]) : unit_grid(ps[i], ps[i].n_units);
         if (grid == 0) return ZHIP_E_UNSUPPORTED;
         m.q[i] = ps[i];
         m.g0[i] = (uint32_t)total;

@@ -2605,6 +2605,189 @@ KernelFn select_xw_kernel(bool crc, int item, int swap) {
 }
 #endif
 
+// ---------------------------------------------------------------------------
+// The full-row form of k_decode_il (reported under that name): k_decode_xw's
+// access order -- wave w of a workgroup on chunk 4 G + w of a group of four
+// consecutive batch chunks, lane l's blocks at 1 KiB apart, so one k-step of
+// the workgroup writes the four chunks' rows side by side -- with
+// k_decode_il's per-workgroup costs.  A wave streams kIlxSpans consecutive
+// 8 KiB spans of its chunk in passes of eight blocks (the next pass's loads
+// after the current pass's stores: the codec-free landscape of
+// profiles/r10/ has that order ahead of the two-buffer one); the stride is
+// 1 KiB throughout, so ONE Horner chain per lane runs through all 8 kIlxSpans
+// blocks with A_1024 (the xw tables) and ends on the group's last span, whose
+// lane constant is k_decode_xw's for that span (xw_klane).  Per workgroup one
+// 24 KiB table fill and one lane-multiply column for 4 x 8 kIlxSpans KiB of
+// payload; per wave one reduction (wave_xor, no barrier) and one publication
+// to its own chunk's line: xw / kIlxSpans arrivals per chunk, the count
+// k_decode_il has (32 on the headline; launch_decode admits at most 32, the
+// mask form).  Tables before the data flood, each block's Horner step after
+// its store, statuses, row-map / affine destinations and the fused index
+// checks as k_decode_il.  (CPU emulation: zhip_emulate_chunk_crc_ilx.)
+template <bool CRC, int ITEM, int SWAP, bool AFF>
+__device__ __forceinline__ void ilx_body(const DecodeParams& p, const uint32_t g, const uint32_t G) {
+    constexpr int K = kDefaultBlocks, NP = (int)kIlxSpans;
+    if constexpr (AFF) __builtin_amdgcn_s_setprio(3);  // until the tables are in LDS (k_decode_il's PRIO 4)
+    __shared__ uint32_t s_tab[CRC ? kPairTabWords : 1];
+    __shared__ uint32_t s_mul[CRC ? 12 * kThreads : 1];
+    __shared__ uint32_t s_red[kThreads / 64];
+    const int t = threadIdx.x;
+    const uint32_t l = (uint32_t)t & 63u;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane((uint32_t)t >> 6);
+    const uint32_t wpc = p.xw / (uint32_t)NP;  // workgroups per group of four chunks = arrivals per chunk
+    const uint32_t quad = g / wpc, r = g - quad * wpc;
+    if (quad * 4u >= p.n_chunks && g >= p.n_idx) return;  // workgroup-uniform
+    const uint32_t c = quad * 4u + wv;
+    const bool has = c < p.n_chunks;
+    const uint32_t expected = p.g.nbytes + (CRC ? 4u : 0u);
+    const uint8_t* zero = reinterpret_cast<const uint8_t*>(g_rows_zero);
+    // 1. vector loads in a path-independent order: [CRC: tables (6), the lane
+    //    constant, the index lane constant, the first index block], the first
+    //    pass's K data blocks; headers, row-map entries and the trailer are scalar
+    uint4 tv0, tv1, tv2, tv3, tv4, tv5;
+    uint32_t kl = 0, kix = 0;
+    if constexpr (CRC) {
+        const uint4* gt = reinterpret_cast<const uint4*>(p.xw_tab);
+        tv0 = gt[t];
+        tv1 = gt[t + kThreads];
+        tv2 = gt[t + 2 * kThreads];
+        tv3 = gt[t + 3 * kThreads];
+        tv4 = gt[t + 4 * kThreads];
+        tv5 = gt[t + 5 * kThreads];
+        kl = load_u32_any(reinterpret_cast<const uint8_t*>(p.xw_klane + ((size_t)r * NP + (NP - 1)) * 64u + l));
+        kix = load_u32_any(reinterpret_cast<const uint8_t*>(p.xw_kidx + t));
+    }
+    Unit U;
+    if (has) U = resolve_unit(p, c * p.nseg, expected);
+    else {
+        U.c = 0;
+        U.sidx = 0;
+        U.mode = ZHIP_ST_MISSING;
+        U.cp = zero;
+        U.seg_lo = 0;
+        U.sel = 0;
+        U.out_off = 0;
+    }
+    const bool ok = has && U.mode == ZHIP_ST_OK;
+    const int32_t lo_frame = (int32_t)p.E - (int32_t)(p.nseg * p.seg);  // a multiple of 4096 (whole rows)
+    const int32_t span0 = lo_frame + 8192 * (int32_t)(r * (uint32_t)NP);
+    uint4 ipre = make_uint4(0, 0, 0, 0);
+    if constexpr (CRC) ipre = index_prefetch(p, g, g < p.n_idx, t, zero);
+    uint4 A[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int32_t base = span0 + 1024 * k;
+        A[k] = load_stream16_any(ok && base >= 0 ? U.cp + base + 16 * l : zero);
+    }
+    if constexpr (AFF) __builtin_amdgcn_s_setprio(0);
+    // destinations of the 2 NP 4 KiB steps (scalar, consumed at the stores)
+    zhip_rowblk m[2 * NP];
+    if (AFF && (!has || sel_whole(p, U.sel))) {
+#pragma unroll
+        for (int h = 0; h < 2 * NP; ++h) m[h] = aff_rowblk(p, 2u * (uint32_t)NP * r + (uint32_t)h);
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2 * NP; ++h) {
+            const uint32_t st = 2u * (uint32_t)NP * r + (uint32_t)h;
+            const uint32_t sidx = p.nseg - 1u - st / (uint32_t)K;
+            m[h] = load_uniform<zhip_rowblk>(p.rowmap + ((size_t)U.sel * p.nseg + sidx) * K + (st % (uint32_t)K));
+        }
+    }
+    uint32_t stored = 0;
+    if (CRC && ok) stored = load_trailer_uniform(U.cp, p.g.nbytes);
+    // 2. tables into LDS, the lane-multiply column
+    if constexpr (CRC) {
+        uint4* stt = reinterpret_cast<uint4*>(s_tab);
+        stt[t] = tv0;
+        stt[t + kThreads] = tv1;
+        stt[t + 2 * kThreads] = tv2;
+        stt[t + 3 * kThreads] = tv3;
+        stt[t + 4 * kThreads] = tv4;
+        stt[t + 5 * kThreads] = tv5;
+        lanemul3_init(s_mul, t, kl);
+        __syncthreads();
+    }
+    if (has) {
+        // 3. NP passes: stores, each block's Horner step after its store, then
+        //    the next pass's loads
+        uint8_t* sink = reinterpret_cast<uint8_t*>(g_rows_sink);
+        const bool writes = ok || U.mode == ZHIP_ST_MISSING;
+        uint8_t* const obase = p.out + U.out_off;
+        const uint4 f = make_uint4(p.fill[0], p.fill[1], p.fill[2], p.fill[3]);
+        const uint32_t rmask = (1u << p.row_shift) - 1u;
+        Acc4 acc = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int pp = 0; pp < NP; ++pp) {
+            if (pp != 0) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const int32_t base = span0 + 8192 * pp + 1024 * k;
+                    A[k] = load_stream16_any(ok && base >= 0 ? U.cp + base + 16 * l : zero);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const zhip_rowblk& mk = m[2 * pp + (k >> 2)];
+                const uint32_t o = 1024u * (uint32_t)(k & 3) + 16u * l;  // byte in the 4 KiB step
+                const uint32_t lane_row = o >> p.row_shift;
+                const bool wr = writes && lane_row - mk.lo < mk.hi - mk.lo;
+                const int64_t lane_off = (int64_t)lane_row * p.r_oy + (int64_t)(o & rmask);
+                store_nt16(wr ? obase + mk.rel + lane_off : sink, ok ? swap_block<ITEM, SWAP>(A[k]) : f);
+                if (CRC && ok) crc_block4(s_tab, acc, A[k]);
+            }
+        }
+        // 4. run end: one chain per lane, one publication per wave
+        if constexpr (CRC) {
+            uint32_t v = ok ? lanemul3(s_mul, t, fold4(s_tab, acc)) : 0u;
+            v = wave_xor(v);
+            if (ok)
+                publish_il(p, c, r, wpc, __builtin_amdgcn_readfirstlane(v), __builtin_amdgcn_readfirstlane(stored),
+                           (int)l, kPubLine / 2u);
+        }
+        if (r == 0) unit_status_pair(p, U, CRC, (int)l);
+    }
+    // 5. fused shard-index checks (one step per lane), the first block prefetched
+    if constexpr (CRC)
+        for (uint32_t j = g; j < p.n_idx; j += G) verify_index_pair(p, j, t, kix, s_tab, s_red, j == g, ipre);
+}
+
+// (the grid of one launch alone: measured, 27.7 against 25.9 us on the headline,
+// and not dispatched -- launch_decode takes the form in fused launches only)
+template <bool CRC, int ITEM, int SWAP, bool AFF>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_decode_ilx(const DecodeParams p) {
+    ilx_body<CRC, ITEM, SWAP, AFF>(p, blockIdx.x, gridDim.x);
+}
+
+// the full-row grids of m.n independent launches back to back in one grid
+// (k_decode_il_multi's scheme)
+template <bool CRC, int ITEM, int SWAP, bool AFF>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_decode_ilx_multi(const MultiParams m) {
+    const uint32_t b = blockIdx.x;
+    uint32_t i = 0;
+#pragma unroll
+    for (uint32_t k = 1; k < ZHIP_MULTI_MAX; ++k) i += (k < m.n && b >= m.g0[k]) ? 1u : 0u;
+    ilx_body<CRC, ITEM, SWAP, AFF>(m.q[i], b - m.g0[i], m.g0[i + 1] - m.g0[i]);
+}
+
+KernelFn select_ilx_kernel(bool crc, int item, int swap, bool aff) {
+    if (!crc) return nullptr;
+    return for_item(item, swap, [&](auto t) -> KernelFn {
+        using T = decltype(t);
+        return aff ? k_decode_ilx<true, T::item, T::swap, true> : k_decode_ilx<true, T::item, T::swap, false>;
+    });
+}
+
+MultiFn select_ilx_multi_kernel(bool crc, int item, int swap, bool aff) {
+    if (!crc) return nullptr;
+    return for_item(item, swap, [&](auto t) -> MultiFn {
+        using T = decltype(t);
+        return aff ? k_decode_ilx_multi<true, T::item, T::swap, true>
+                   : k_decode_ilx_multi<true, T::item, T::swap, false>;
+    });
+}
+
 KernelFn select_duo_kernel(bool crc, int item, int swap) {
     return for_item(item, swap, [&](auto t) -> KernelFn {
         using T = decltype(t);

@@ -56,7 +56,11 @@ constexpr int kByteTabWords = 2048;
 extern const char* g_last_kernel;  // zhip_last_kernel: the kernel the last decode / mapped encode launched
 extern uint32_t g_last_grid;       // zhip_last_grid: that launch's workgroups (fire)
 constexpr uint32_t kIlwMaxUnits = 512;  // k_decode_ilw (512 lanes) for grids of at most 2 units per CU
-constexpr int kIlBasisWords = 64;  // T1 / T2 / T3 bases (11 + 11 + 10, padded to 32), A4 bases (4 x 8)
+// k_decode_il's full-row form: 8 KiB spans a wave streams per workgroup (32 arrivals per 1 MiB chunk, as
+// k_decode_il's 32 KiB units; 512 workgroups per headline program.  Two spans -- 1 024 workgroups, 64 arrivals --
+// copy 0.5 us slower in the codec-free landscape, profiles/r10/)
+constexpr uint32_t kIlxSpans = 4;
+constexpr int kIlBasisWords = 64; // T1 / T2 / T3 bases (11 + 11 + 10, padded to 32), A4 bases (4 x 8)
 
 // What k_decode_lead (and the k_decode_il arm) need before their first vector loads,
 // FIRST in the kernel arguments and read as one scalar batch (pair_hot): the
@@ -268,7 +272,8 @@ constexpr uint32_t kTuneDeferB = 33554432u;   // k_decode_pair arm: unit B's loa
 constexpr uint32_t kTuneIl = 67108864u;       // whole-row layouts: k_decode_il wherever the layout admits it
 constexpr uint32_t kTuneNoIl = 134217728u;    // whole-row layouts: never k_decode_il (k_decode_pair)
 constexpr uint32_t kTuneXw = 268435456u;      // whole-row layouts: k_decode_xw where admitted
-constexpr uint32_t kTuneNoXw = 536870912u;    // whole-row layouts: never k_decode_xw
+constexpr uint32_t kTuneNoXw = 536870912u;    // whole-row layouts: never k_decode_xw, nor k_decode_il's full-row form
+                                              // (any tuning bit or arm keeps the interleaved k_decode_il: the A/B knob)
 constexpr uint32_t kTuneNoPub = 1073741824u;  // timing arm: k_decode_il / k_decode_xw skip the CRC publication
 constexpr uint32_t kTuneIlLean = 16384u;    // k_decode_il arm: lean predicted prologue (data loads before the header chain)
 constexpr uint32_t kTuneTile4F = 2147483648u;   // transposed layouts arm: k_decode_tile4f where the layout admits it
@@ -522,6 +527,8 @@ KernelFn select_pair_kernel(bool crc, int item, int swap, PairForm form);
 KernelFn select_duo_kernel(bool crc, int item, int swap);
 KernelFn select_il_kernel(bool crc, int item, int swap, bool aff);
 MultiFn select_il_multi_kernel(bool crc, int item, int swap, bool aff);  // k_decode_il_multi, the same forms
+KernelFn select_ilx_kernel(bool crc, int item, int swap, bool aff);      // k_decode_il's full-row form (CRC only)
+MultiFn select_ilx_multi_kernel(bool crc, int item, int swap, bool aff);
 KernelFn select_ilw_kernel(int item, int swap, IlwForm form, bool lmr, bool aff);
 KernelFn select_ilh_kernel(int item, int swap, bool lb, bool aff);
 #if ZHIP_TUNING

@@ -347,6 +347,8 @@ def lib():
     L.zhip_emulate_chunk_crc_il.restype = ctypes.c_uint32
     L.zhip_emulate_chunk_crc_xw.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.zhip_emulate_chunk_crc_xw.restype = ctypes.c_uint32
+    L.zhip_emulate_chunk_crc_ilx.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+    L.zhip_emulate_chunk_crc_ilx.restype = ctypes.c_uint32
     L.zhip_plan_table_image.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64]
     L.zhip_plan_table_image.restype = ctypes.c_uint64
     L.zhip_plan_table_offsets.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
@@ -439,6 +441,12 @@ class Plan:
         fn = lib().zhip_emulate_chunk_crc_il if pair == "il" else lib().zhip_emulate_chunk_crc_xw if pair == "xw" else \
             lib().zhip_emulate_chunk_crc_pair if pair else lib().zhip_emulate_chunk_crc
         return int(fn(self._h, buf))
+
+    def emulate_chunk_crc_fullrow(self, data: bytes, spans: int) -> int:
+        """k_decode_il's full-row decomposition with `spans` 8 KiB spans per
+        lane chain (the decode takes 4).  Test hook."""
+        buf = ctypes.create_string_buffer(bytes(data) + b"\0" * 16)
+        return int(lib().zhip_emulate_chunk_crc_ilx(self._h, buf, spans))
 
     def table_image(self, which: int) -> np.ndarray:
         """The table image zhip_plan_upload puts on the device, built on the host
