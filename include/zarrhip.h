@@ -517,6 +517,18 @@ int zhip_debug_stamps(uint64_t *host_out, uint32_t n_wg);
  * from the fill value under NDBuffer.all_equal rules, else 0 (every launch
  * writes every flag: kernels that OR flags are preceded by an async zeroing
  * of d_nonempty on the same stream).
+ * d_workspace holds max(4, workspace_words) (zhip_plan_info) * n_chunks uint32
+ * words (8-byte aligned), zeroed by the caller before the FIRST launch only.
+ * The encode kernels keep their per-chunk arrival state there -- the XOR of
+ * the CRC contributions with arrival bits, non-empty bits or a ticket count --
+ * and the arrival that completes a chunk stores zero back into every word it
+ * used (kernels that own their chunks whole, and layouts without a checksum
+ * under the kernels that OR the flags, never touch it): every launch leaves
+ * the whole workspace zero.  With d_status and d_nonempty rewritten in full by
+ * every launch -- whatever they held -- the same arguments can be launched
+ * again over a changed `arr`, eagerly or from a captured graph, without any
+ * action by the caller; launches that may overlap need a workspace, a status
+ * table and flags each.
  * ZHIP_DF_FAST_ROWS: every chunk selects whole rows that are contiguous and
  * 16-byte aligned in arr.  Asynchronous. */
 int zhip_encode(const zhip_plan *plan, const void *arr, void *dst, const zhip_chunk *d_chunks,

@@ -56,8 +56,13 @@ def _upload(arr: np.ndarray, device):
 
 class EncodeLaunch:
     """One zhip_encode launch over flat chunk tables.  Every launch writes every
-    chunk's non-empty flag (the library zeroes the flags itself before a kernel
-    that ORs them, include/zarrhip.h), so a prepared launch can be replayed."""
+    chunk's status and non-empty flag (the library zeroes the flags itself
+    before a kernel that ORs them) and leaves the workspace, zeroed here once,
+    all zero again (the completing arrival of each chunk resets the words it
+    used: include/zarrhip.h, zhip_encode), so a prepared launch can be replayed
+    over a changed source, eagerly or from a captured graph, with nothing to
+    reset in between (tests/test_gpu_encode_replay.py); launches that may
+    overlap need an EncodeLaunch each."""
 
     def __init__(self, layout: N.Layout, chunks: np.ndarray, sels: np.ndarray, arr, dst, fast: bool,
                  device, rows: bool = False, tile: bool = False, tile_prefix: bool = False):
