@@ -124,7 +124,12 @@ typedef struct zhip_layout {
     uint8_t fill[16];                  /* fill value bytes, native order              */
 } zhip_layout;
 
-/* One chunk (decode unit) of a batch. */
+/* One chunk (decode unit) of a batch.  For a decode `src` may be ANY byte
+ * offset: no alignment is assumed of an encoded chunk, of a shard blob, of the
+ * (offset, nbytes) entries of its index, of the inner chunks they name (any
+ * order, gaps, two entries naming the same bytes) or of a CRC trailer.  The
+ * kernels choose their load form per chunk from the address they find
+ * (tests/placement_cases.py is the table that holds them to it). */
 typedef struct zhip_chunk {
     uint64_t src;      /* byte offset in src: encoded chunk | shard blob (SHARDED) */
     uint64_t src_len;  /* encoded chunk length | shard blob length                 */
@@ -334,6 +339,10 @@ int zhip_plan_upload(zhip_plan *plan);
 
 /* Decode `n_chunks` chunks of `src` (device) into `out` (device).
  * src must stay readable for 64 bytes past src_size (loads are 16-byte wide).
+ * Chunks, index entries and trailers may sit at any byte address inside src:
+ * a launch reads no further than 3 bytes before one (the aligned dwords that
+ * cover an unaligned entry or trailer) and 64 bytes past its end, so a chunk
+ * at offset 0 of src needs 3 readable bytes before src.
  * d_chunks/d_sels/d_status/d_workspace/d_errflag are device pointers;
  * d_workspace holds workspace_words (zhip_plan_info; 4 for most layouts) * n_chunks zeroed
  * uint32 words (8-byte aligned) (self-resetting: keep it
